@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """bench.py -- YOND hot path on MI355X: Bayer megapixels/s end-to-end (NLE + VST + denoise + iVST).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times EXACTLY K steps and prints the headline line (`ms_per_step`: one timed step).
+`--full` adds everything else the line can carry: HIP events and clock sampling inside the timed region, rooflines, the
+sequential / iter / fp32-mfma / other-config legs, the CPU baseline and the parity check against the oracle.
+`--dump-outputs DIR` writes what the last timed step handed its caller to DIR/*.npy (OutputDump; the inputs are seeded).
 
 `--gpus N` with N > 1 and no torchrun environment: this process starts
 `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a CHILD (before anything touches the GPU) and
@@ -14,7 +19,7 @@ span >= 2 s): per frame the self-calibrated noise-level estimation, bias-LUT bui
 `--precision fp32-mfma` keeps them on the fp32-input MFMA), inverse VST + unpack.  'once' pipelines stream the frames
 through pipeline.denoise_stream (NLE of frame k+1 on a second HIP stream under the convolutions of frame k); the
 per-frame latency of SURVEY section 8d (one frame at a time, resident -> resident) is measured right behind the timed region
-and reported as `sequential` on the same line.  `--mode iter`: the shipped two-round pipeline (YOND_SIDD.py:419-472), one
+and reported as `sequential` on the same line (--full).  `--mode iter`: the shipped two-round pipeline (YOND_SIDD.py:419-472), one
 frame at a time, asserted to run BOTH rounds.  Frames are sharded one stream per GPU (image parallel, weak scaling);
 there is no data-path collective, the only RCCL traffic is the barrier / max-over-ranks of the timing and the final
 PSNR reduction.  Prints ONE JSON line on rank 0.
@@ -74,7 +79,15 @@ def parse_args(argv=None):
     ap.add_argument("--precision", default=None, choices=["fp32", "fp32-mfma", "fp16"],
                     help="fp32 (headline): fp32 results, 3x3 convolutions as fp32-accurate split-operand products on the fp16 MFMA; "
                          "fp32-mfma: every convolution on the fp32-input MFMA; fp16: BASELINE cfg 5 (not the headline configuration)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: HIP events and clock sampling in the timed region, rooflines, the sequential / "
+                         "iter / fp32-mfma / other-config legs, the CPU baseline and the parity check against the oracle "
+                         "(--no-extras, --no-cpu-baseline and --no-kernel-events trim a --full run)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step handed its caller as DIR/<name>.npy (OutputDump)")
     a = ap.parse_args(argv)
+    if not a.full:                                     # a plain run: set up, warm up, time the steps, print the headline
+        a.no_extras = a.no_cpu_baseline = a.no_kernel_events = True
     if a.cfg == 3:
         a.mode = "iter"                                # the shipped SIDD runfile (runfiles/YOND/SIDD_simple+full_pre_grumix.yml)
         a.height, a.width = 256, 8192                  # the 32 blocks of an item side by side: the denoised Bayer pixels
@@ -311,9 +324,10 @@ def sidd_eval_group(items, net, arch, P):
     return ress
 
 
-def sidd_eval_stream(items, group, net, arch, P):
+def sidd_eval_stream(items, group, net, arch, P, each=None):
     """YOND_SIDD.eval's loop over `items` as the driver runs it: groups of `group` images, consecutive groups overlapped on two HIP streams
-    (pipeline.denoise_stream_groups), the block metrics of a finished group on a third.  Returns the last image's result."""
+    (pipeline.denoise_stream_groups), the block metrics of a finished group on a third.  Returns the last image's result; `each(res)` sees
+    every image's."""
     groups = [items[i:i + group] for i in range(0, len(items), group)]
     met = {}
 
@@ -326,19 +340,100 @@ def sidd_eval_stream(items, group, net, arch, P):
                 raise SystemExit(f"bench.py: the SIDD pipeline ran {len(res['raw_dns'])} pass(es), expected 2 (regs {res['regs']})")
             res['metrics'] = m
             last = res
+            if each:
+                each(res)
     return last
 
 
-def batch_stream(frames, B, net, arch, pipe, P):
+def batch_stream(frames, B, net, arch, pipe, P, each=None):
     """cfg 4's loop: B frames per forward, the B estimators of batch k+1 on a second HIP stream under the batched network pass of batch k
-    (pipeline.denoise_stream_batches).  Returns the LAST batch in IterDenoiseBatch's shape (raw_dns [[B][H][W]], regs [[B]], params [[B]])."""
+    (pipeline.denoise_stream_batches).  Returns the LAST batch in IterDenoiseBatch's shape (raw_dns [[B][H][W]], regs [[B]], params [[B]]);
+    `each(r)` sees every frame's result."""
     import torch
     last = []
     for r in P.denoise_stream_batches(frames, B, net, arch, pipe):
+        if each:
+            each(r)
         last.append(r)
         if len(last) > B:
             last.pop(0)
     return dict(raw_dns=[torch.stack([r['raw_dns'][0] for r in last])], regs=[[r['regs'][0] for r in last]], params=[[r['params'][0] for r in last]])
+
+
+def _flat64(x):
+    """A result's small per-frame values (regs, params, block metrics: numbers, arrays, tensors, nested lists) as one float64 vector."""
+    import numpy as np
+    import torch
+    if isinstance(x, torch.Tensor):
+        return x.detach().double().cpu().reshape(-1).numpy()
+    if isinstance(x, dict):
+        x = [x[k] for k in sorted(x)]
+    if isinstance(x, (list, tuple)):
+        parts = [_flat64(v) for v in x]
+        return np.concatenate(parts) if parts else np.zeros(0)
+    if x is None:
+        return np.full(1, np.nan)
+    return np.asarray(x, np.float64).reshape(-1)
+
+
+class OutputDump:
+    """--dump-outputs DIR: what the timed path handed its caller in the LAST timed step, result by result in the order it yielded them, so
+    that two builds run with the same arguments (the same seeded inputs) can be compared output for output.  Per pass p:
+    raw_dn_pass{p}.npy  float32 [results][k]: the denoised pixels at k fixed, seeded positions (every pixel where the step's output fits in
+                        SAMPLE_BYTES; otherwise the same fraction of every output)
+    raw_dn_pass{p}_sum.npy  float64 [results]: the sum over ALL pixels of each output
+    and params.npy / regs.npy (/ metrics.npy for cfg 3) float64 [results][m]: each result's values flattened (NaN-padded if ragged).
+    The samples are gathered on the device as the results are yielded, so the step's outputs are never held beyond the path's own use."""
+    SAMPLE_BYTES = 48 << 20
+
+    def __init__(self, out_dir, px_per_step, dev, sample_bytes=SAMPLE_BYTES):
+        self.dir, self.dev = out_dir, dev
+        self.q = min(1.0, (sample_bytes // 4) / max(px_per_step, 1))
+        self.idx = {}
+        self.rows = []
+
+    def index(self, n):
+        """The fixed sample positions of an output of n pixels (built before the timed region for the shapes the run yields)."""
+        import numpy as np
+        import torch
+        if n not in self.idx:
+            k = max(1, min(n, int(n * self.q)))
+            sel = np.arange(n) if k == n else np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+            self.idx[n] = torch.from_numpy(sel).to(self.dev)
+        return self.idx[n]
+
+    def add(self, res):
+        import torch
+        dns = res['raw_dns']
+        self.rows.append({'samples': [d.reshape(-1).index_select(0, self.index(d.numel())) for d in dns],
+                          'sums': [d.sum(dtype=torch.float64) for d in dns],
+                          'params': res.get('params'), 'regs': res.get('regs'), 'metrics': res.get('metrics')})
+
+    def write(self):
+        import numpy as np
+        import torch
+        os.makedirs(self.dir, exist_ok=True)
+        files = {}
+
+        def save(name, arrs, dtype):
+            arrs = [np.asarray(v, dtype).reshape(-1) for v in arrs]
+            m = max(len(v) for v in arrs)
+            out = np.full((len(arrs), m), np.nan, dtype)
+            for i, v in enumerate(arrs):
+                out[i, :len(v)] = v
+            np.save(os.path.join(self.dir, name + ".npy"), out)
+            files[name] = list(out.shape)
+
+        for p in range(max(len(r['samples']) for r in self.rows)):
+            rows = [r for r in self.rows if p < len(r['samples'])]
+            save(f"raw_dn_pass{p}", [r['samples'][p].float().cpu().numpy() for r in rows], np.float32)
+            sums = torch.stack([r['sums'][p] for r in rows]).cpu().numpy()
+            np.save(os.path.join(self.dir, f"raw_dn_pass{p}_sum.npy"), sums)
+            files[f"raw_dn_pass{p}_sum"] = list(sums.shape)
+        for key in ('params', 'regs', 'metrics'):
+            if any(r[key] is not None for r in self.rows):
+                save(key, [_flat64(r[key]) for r in self.rows], np.float64)
+        return {"dir": self.dir, "results": len(self.rows), "sample_fraction": round(self.q, 6), "files": files}
 
 
 def timed_region(run_step, steps, sync, D, dev):
@@ -475,25 +570,34 @@ def main(argv=None):
                              f"(regs {res['regs']}): with --weights procedural the reference's guard ends round 2")
         return res
 
-    def run(nframes, sequential=False):
-        """nframes passes of the hot path over the resident frames (cycled)."""
+    def run(nframes, sequential=False, each=None):
+        """nframes passes of the hot path over the resident frames (cycled); `each(res)` sees every result the path yields."""
         last = None
         if a.batch and not sequential and not a.sequential and a.mode == "once":
-            last = batch_stream((frames[i % len(frames)] for i in range(nframes // a.batch * a.batch)), a.batch, net, arch, pipe, P)
+            last = batch_stream((frames[i % len(frames)] for i in range(nframes // a.batch * a.batch)), a.batch, net, arch, pipe, P, each=each)
         elif a.batch:
             for b in range(nframes // a.batch):
                 last = P.IterDenoiseBatch([frames[(b * a.batch + j) % len(frames)] for j in range(a.batch)], net, arch, pipe)
+                if each:
+                    each(last)
         elif stream_driver and not sequential:
             for last in P.denoise_stream((frames[i % len(frames)] for i in range(nframes)), net, arch, pipe):
-                pass
+                if each:
+                    each(last)
         elif a.cfg == 3 and a.group > 1 and not sequential and not a.sequential:
-            last = sidd_eval_stream([frames[i % len(frames)] for i in range(nframes)], a.group, net, arch, P)
+            last = sidd_eval_stream([frames[i % len(frames)] for i in range(nframes)], a.group, net, arch, P, each=each)
         elif a.cfg == 3 and a.group > 1:
             for i in range(0, nframes, a.group):
-                last = sidd_eval_group([frames[(i + j) % len(frames)] for j in range(min(a.group, nframes - i))], net, arch, P)[-1]
+                ress = sidd_eval_group([frames[(i + j) % len(frames)] for j in range(min(a.group, nframes - i))], net, arch, P)
+                last = ress[-1]
+                if each:
+                    for r in ress:
+                        each(r)
         else:
             for i in range(nframes):
                 last = one(frames[i % len(frames)])
+                if each:
+                    each(last)
         return last
 
     # warm-up: W steps, continued until --min-warmup-s has passed (clocks and caches settle)
@@ -508,7 +612,7 @@ def main(argv=None):
     torch.cuda.synchronize()
     D.barrier()
     torch.cuda.synchronize()
-    # HIP events (on the launch stream) bracket the launches of the 3x3 stride-1 convolution kernels -- the dominant
+    # --full: HIP events (on the launch stream) bracket the launches of the 3x3 stride-1 convolution kernels -- the dominant
     # family: 18 launches per forward, 91 % of the MACs -- in every 4th forward of the timed region; an event pair costs
     # the stream a few microseconds (reported: `without_kernel_events`), so the other kernels and the VST / NLE stages are
     # timed in one more, instrumented pass behind it
@@ -516,25 +620,33 @@ def main(argv=None):
     plan.prof = None if a.no_kernel_events else []
     plan.prof_only = is33
     plan.prof_every = 4                  # every 4th forward carries the event pairs (their cost is reported: `without_kernel_events`)
-    sclk = GpuSampler() if rank == 0 else None
+    sclk = GpuSampler() if (rank == 0 and a.full) else None
     if sclk:
         sclk.start()
-    # in-kernel shader clock of the split-operand convolution launches of the timed region: workgroup 0 of every launch adds its
+    # in-kernel shader clock of the split-operand convolution launches of the timed region (--full): workgroup 0 of every launch adds its
     # elapsed shader cycles and 100 MHz reference ticks to two device counters (YondConvDesc.clk).  (A probe kernel BESIDE the
     # region cannot be used: these kernels take every vector register of their CUs, so a single foreign wave keeps one of the
     # 256 persistent workgroups waiting for a CU -- measured: every launch 1.45x longer.)
-    plan.clk = torch.zeros(2, dtype=torch.int64, device=dev)
+    plan.clk = torch.zeros(2, dtype=torch.int64, device=dev) if a.full else None
     last_res = {}
+    dump = None
+    if a.dump_outputs and rank == 0:
+        dump = OutputDump(a.dump_outputs, F * n_pass * H * W, dev)
+        for n in {H * W, (a.batch or 1) * H * W}:             # (the sample positions of the shapes the path yields, built before the clock starts)
+            dump.index(n)
+    steps_done = [0]
 
     def run_step():
-        last_res['res'] = run(F)
+        steps_done[0] += 1
+        last_res['res'] = run(F, each=dump.add if (dump and steps_done[0] == a.steps) else None)
     elapsed, per_rank_s = timed_region(run_step, a.steps, torch.cuda.synchronize, D, dev)
     res = last_res['res']
+    dumped = dump.write() if dump else None
     sclk_res = sclk.result() if sclk else None
-    clk_c, clk_r = (int(v) for v in plan.clk.cpu())
+    clk_c, clk_r = (int(v) for v in plan.clk.cpu()) if plan.clk is not None else (0, 0)
     plan.clk = None
-    per_rank_mhz = D.gather_over_ranks(clk_c / clk_r * 100.0 if clk_r > 0 else 0.0, dev)      # every rank's own in-kernel clock
-    if rank == 0:
+    per_rank_mhz = D.gather_over_ranks(clk_c / clk_r * 100.0 if clk_r > 0 else 0.0, dev) if a.full else [0.0] * world     # every rank's own in-kernel clock
+    if rank == 0 and a.full:
         sclk_res = dict(sclk_res or {}, in_kernel_mhz=round(clk_c / clk_r * 100.0, 1) if clk_r > 0 else None,
                         source="in_kernel_mhz: s_memtime / s_memrealtime of workgroup 0 of every split-operand convolution launch of the "
                                "timed region (YondConvDesc.clk); hwmon_mhz / socket_power_w: sysfs hwmon of the busiest card, 50 ms "
@@ -960,7 +1072,9 @@ def main(argv=None):
             "roofline_vst_nle": roof_hbm,
             "conv_stack": {"ms_per_frame": round(conv_ms, 3), "tflops": round(conv_fl / (conv_ms * 1e-3) / 1e12, 2) if conv_ms else None,
                            "share_of_frame": round(conv_ms / (elapsed / n_timed * 1e3), 3) if conv_ms else None,
-                           "measured": "HIP events around every convolution launch, the median of three instrumented passes after the timed region"},
+                           "measured": "HIP events around every convolution launch, the median of three instrumented passes after the timed region"}
+                          if a.full else None,
+            "full": a.full,
             "psnr_vs_clean_db": {"denoised": round(red["psnr_last"], 3), "noisy_input": round(10 * np.log10(1.0 / mse_in), 3)},
             "estimated_K_sigma": [[round(float(v), 4) for v in pr] for pr in (res['params'] if not a.batch else res['params'][-1])],
             **({"images_per_s": round(world * n_timed / elapsed, 2), "ms_per_image": round(elapsed / n_timed * 1e3, 3),
@@ -977,6 +1091,8 @@ def main(argv=None):
                                           for r, (t, m) in enumerate(zip(per_rank_s, per_rank_mhz))]),
             "static_notes": static_notes(),
         }
+        if dumped:
+            out["outputs"] = dumped
         if world == 1 and not a.no_cpu_baseline and not a.batch:
             out["cpu_baseline"], out["parity_vs_oracle"] = cpu_baseline_and_parity(a, arch, dev, make_net)
         print(json.dumps(out), flush=True)

@@ -1,5 +1,5 @@
 """CPU: bench.py's launcher logic -- `--gpus N` without a torchrun environment starts N ranks as a CHILD job (before any
-GPU call); an inconsistent environment is refused."""
+GPU call); an inconsistent environment is refused; a plain run against --full; the --dump-outputs writer."""
 import os
 import sys
 
@@ -55,6 +55,54 @@ def test_config_shortcuts():
     assert a.precision == "fp16" and (a.height, a.width) == (4000, 6000)
     a = bench.parse_args([])
     assert a.precision == "fp32" and a.frames_per_step == 24 and a.mode == "once"
+
+
+def test_plain_run_is_the_headline_only():
+    """A plain run times the headline alone; --full brings back every leg, and --no-extras / --no-cpu-baseline /
+    --no-kernel-events still trim a --full run."""
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not a.full and a.no_extras and a.no_cpu_baseline and a.no_kernel_events and a.steps == 7 and a.dump_outputs is None
+    a = bench.parse_args(["--full"])
+    assert a.full and not a.no_extras and not a.no_cpu_baseline and not a.no_kernel_events
+    a = bench.parse_args(["--full", "--no-cpu-baseline"])
+    assert a.no_cpu_baseline and not a.no_extras
+    assert bench.parse_args(["--dump-outputs", "d"]).dump_outputs == "d"
+
+
+def test_output_dump_files(tmp_path):
+    """OutputDump on CPU tensors: one row per result in yield order, float32 samples at fixed seeded positions (the same
+    positions in a second dump), float64 sums over every pixel and float64 per-result values, the whole under 64 MB."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    outs = [[torch.rand(300, 400, generator=g) for _ in range(2)] for _ in range(3)]
+    dumps = []
+    for k, cap in enumerate((1 << 30, 3 * 300 * 400 * 4 // 2)):
+        d = bench.OutputDump(str(tmp_path / str(k)), 3 * 2 * 300 * 400, torch.device("cpu"), sample_bytes=cap)
+        for i, dns in enumerate(outs):
+            d.add({'raw_dns': dns, 'regs': [(0.5 * i, 1.0)], 'params': [(np.float64(4.0 + i), np.float64(6.0))]})
+        info = d.write()
+        assert info["results"] == 3
+        dumps.append({n: np.load(tmp_path / str(k) / (n + ".npy")) for n in info["files"]})
+    full, half = dumps
+    for p in range(2):
+        x = full[f"raw_dn_pass{p}"]
+        assert x.dtype == np.float32 and x.shape == (3, 300 * 400)
+        np.testing.assert_array_equal(x, np.stack([o[p].reshape(-1).numpy() for o in outs]))
+        s = full[f"raw_dn_pass{p}_sum"]
+        assert s.dtype == np.float64 and s.shape == (3,)
+        np.testing.assert_allclose(s, [o[p].double().sum().item() for o in outs], rtol=1e-12)
+        y = half[f"raw_dn_pass{p}"]
+        assert y.dtype == np.float32 and y.shape == (3, 300 * 400 // 4)
+        assert np.isin(y[0], x[0]).all()                               # a sample of the same output
+        np.testing.assert_array_equal(half[f"raw_dn_pass{p}_sum"], s)  # the sums still cover every pixel
+    np.testing.assert_array_equal(full["params"], [[4.0, 6.0], [5.0, 6.0], [6.0, 6.0]])
+    assert full["regs"].dtype == np.float64 and full["regs"].shape == (3, 2)
+    assert sum(f.stat().st_size for f in tmp_path.rglob("*.npy")) < 64 << 20
 
 
 def _run_stub(args, extra_env=None, timeout=240):

@@ -301,6 +301,42 @@ def test_bench_one_rank_under_torchrun_runs_rccl(tmp_path):
     assert r["collectives"]["all_reduce"] >= 2 and r["collectives"]["barrier"] >= 2
 
 
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """A plain `bench.py` run (no --full): exactly --steps timed steps, the headline keys and none of the --full legs; with
+    --dump-outputs it writes what its last timed step yielded, frame by frame, and that is what IterDenoise computes for the
+    same seeded frames (to the rounding of the estimator's atomic float64 sums, as in tests/test_hip_pipeline.py)."""
+    import yond_public_amd.pipeline as P
+    import yond_public_amd.archs as A
+    import yond_public_amd.synthetic as S
+    H, W, F = 256, 320, 4
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--min-warmup-s", "0",
+                          "--height", str(H), "--width", str(W), "--frames-per-step", str(F), "--dump-outputs", str(tmp_path / "out")],
+                         cwd=str(tmp_path), capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    r = json.loads(lines[0])
+    assert r["steps"] == 2 and r["ms_per_step"] > 0 and r["value"] > 0 and r["unit"] == "Bayer MP/s" and r["higher_is_better"] is True
+    assert r["full"] is False and "cpu_baseline" not in r and r["sequential"] is None and r["roofline"] is None and r["other_configs"] is None
+    assert r["outputs"]["results"] == F and r["outputs"]["sample_fraction"] == 1.0
+    got = np.load(tmp_path / "out" / "raw_dn_pass0.npy")
+    sums = np.load(tmp_path / "out" / "raw_dn_pass0_sum.npy")
+    params = np.load(tmp_path / "out" / "params.npy")
+    assert got.dtype == np.float32 and got.shape == (F, H * W) and sums.dtype == np.float64 and params.dtype == np.float64
+    import bench
+    arch = bench.ARCHS['GuidedResUnet']
+    net = A.GuidedResUnet(dict(arch, precision='fp32'))
+    net.load_state_dict(S.denoising_state_dict(net, 0))
+    net = net.to(DEV).eval()
+    pipe = {'k': 29, 'vst_type': 'exact', 'bias_corr': 'pre', 'iter': 'once', 'max_iter': 1, 'full_dn': True, 'collab_sidd256': False}
+    for i in range(F):                                     # the step's frames: the three distinct frames cycled
+        want = P.IterDenoise(torch.from_numpy(S.synth_noisy(H, W, 4.0, 6.0, i % 3)[0]).to(DEV), net, arch, pipe)
+        dn = want['raw_dns'][0].cpu().numpy()
+        assert np.abs(got[i] - dn.reshape(-1)).max() <= 5e-6
+        assert abs(sums[i] - dn.astype(np.float64).sum()) <= 5e-6 * dn.size
+        np.testing.assert_allclose(params[i], np.asarray(want['params'], np.float64).reshape(-1), rtol=1e-8)
+
+
 def test_yond_sidd_one_rank_under_torchrun_runs_rccl(tmp_path):
     """`YOND_SIDD.py -m eval --synthetic 2` under torchrun --nproc-per-node 1: the metric reduction is an RCCL all-reduce."""
     out = _torchrun_one_rank([os.path.join(ROOT, "YOND_SIDD.py"), "-f", RUNFILE, "-m", "eval", "--synthetic", "2"], tmp_path, 29542)

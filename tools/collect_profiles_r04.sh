@@ -4,21 +4,21 @@
 set -x
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r04; mkdir -p $O
 cd $R
-python bench.py --steps 20 --warmup 5 2>$O/once.err | tail -1 > $O/r04_bench_once.json
-python bench.py --steps 6 --warmup 2 --weights procedural --no-cpu-baseline --no-extras 2>/dev/null | tail -1 > $O/r04_bench_once_procedural_weights.json
-python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-extras 2>/dev/null | tail -1 > $O/r04_bench_once_denoising_weights_same_box.json
-python bench.py --cfg 3 --steps 6 --warmup 2 2>/dev/null | tail -1 > $O/r04_bench_cfg3_sidd.json
-python bench.py --steps 10 --warmup 3 --mode iter --no-cpu-baseline 2>/dev/null | tail -1 > $O/r04_bench_iter.json
-python bench.py --steps 6 --warmup 2 --cfg 4 --no-cpu-baseline 2>/dev/null | tail -1 > $O/r04_bench_cfg4_unet_batch8.json
-python bench.py --steps 6 --warmup 2 --cfg 5 --no-cpu-baseline 2>/dev/null | tail -1 > $O/r04_bench_cfg5_fp16.json
-python bench.py --steps 6 --warmup 2 --precision fp32-mfma --no-cpu-baseline 2>/dev/null | tail -1 > $O/r04_bench_fp32_mfma.json
+python bench.py --full --steps 20 --warmup 5 2>$O/once.err | tail -1 > $O/r04_bench_once.json
+python bench.py --full --steps 6 --warmup 2 --weights procedural --no-cpu-baseline --no-extras 2>/dev/null | tail -1 > $O/r04_bench_once_procedural_weights.json
+python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-extras 2>/dev/null | tail -1 > $O/r04_bench_once_denoising_weights_same_box.json
+python bench.py --full --cfg 3 --steps 6 --warmup 2 2>/dev/null | tail -1 > $O/r04_bench_cfg3_sidd.json
+python bench.py --full --steps 10 --warmup 3 --mode iter --no-cpu-baseline 2>/dev/null | tail -1 > $O/r04_bench_iter.json
+python bench.py --full --steps 6 --warmup 2 --cfg 4 --no-cpu-baseline 2>/dev/null | tail -1 > $O/r04_bench_cfg4_unet_batch8.json
+python bench.py --full --steps 6 --warmup 2 --cfg 5 --no-cpu-baseline 2>/dev/null | tail -1 > $O/r04_bench_cfg5_fp16.json
+python bench.py --full --steps 6 --warmup 2 --precision fp32-mfma --no-cpu-baseline 2>/dev/null | tail -1 > $O/r04_bench_fp32_mfma.json
 python tools/stage_bench.py > $O/r04_stage_kernels.txt 2>&1
 python tools/layer_times.py > $O/r04_layer_times.txt 2>&1
 python tools/wgrad_ab.py > $O/r04_wgrad_ab.txt 2>&1
 python tools/gemm_ab.py > $O/r04_gemm_ab.txt 2>&1
 python tools/train_bench.py --steps 30 > $O/r04_train_bench.txt 2>&1
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --steps 2 --warmup 1 --frames-per-step 4 --no-cpu-baseline --no-extras --min-warmup-s 0"
+B="python3 $R/bench.py --full --steps 2 --warmup 1 --frames-per-step 4 --no-cpu-baseline --no-extras --min-warmup-s 0"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o t -- $B > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o f -- $B > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o w -- $B > /dev/null 2>&1

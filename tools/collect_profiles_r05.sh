@@ -4,12 +4,12 @@
 set -x
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r05; mkdir -p $O
 cd $R
-python bench.py --steps 20 --warmup 5 2>$O/once.err | tail -1 > $O/r05_bench_once.json
-python bench.py --cfg 3 --steps 6 --warmup 2 2>/dev/null | tail -1 > $O/r05_bench_cfg3_sidd.json
-python bench.py --steps 10 --warmup 3 --mode iter --no-cpu-baseline 2>/dev/null | tail -1 > $O/r05_bench_iter.json
-python bench.py --steps 6 --warmup 2 --cfg 4 --no-cpu-baseline 2>/dev/null | tail -1 > $O/r05_bench_cfg4_unet_batch8.json
-python bench.py --steps 6 --warmup 2 --cfg 5 --no-cpu-baseline 2>/dev/null | tail -1 > $O/r05_bench_cfg5_fp16.json
-python bench.py --steps 6 --warmup 2 --precision fp32-mfma --no-cpu-baseline 2>/dev/null | tail -1 > $O/r05_bench_fp32_mfma.json
+python bench.py --full --steps 20 --warmup 5 2>$O/once.err | tail -1 > $O/r05_bench_once.json
+python bench.py --full --cfg 3 --steps 6 --warmup 2 2>/dev/null | tail -1 > $O/r05_bench_cfg3_sidd.json
+python bench.py --full --steps 10 --warmup 3 --mode iter --no-cpu-baseline 2>/dev/null | tail -1 > $O/r05_bench_iter.json
+python bench.py --full --steps 6 --warmup 2 --cfg 4 --no-cpu-baseline 2>/dev/null | tail -1 > $O/r05_bench_cfg4_unet_batch8.json
+python bench.py --full --steps 6 --warmup 2 --cfg 5 --no-cpu-baseline 2>/dev/null | tail -1 > $O/r05_bench_cfg5_fp16.json
+python bench.py --full --steps 6 --warmup 2 --precision fp32-mfma --no-cpu-baseline 2>/dev/null | tail -1 > $O/r05_bench_fp32_mfma.json
 python tools/stage_bench.py > $O/r05_stage_kernels.txt 2>&1
 python tools/layer_times.py > $O/r05_layer_times.txt 2>&1
 python tools/layer_times.py 32 128 128 > $O/r05_layer_times_cfg3.txt 2>&1
@@ -17,7 +17,7 @@ python tools/block0_ab.py > $O/r05_block0_ab.txt 2>&1
 python tools/train_bench.py --steps 30 > $O/r05_train_bench.txt 2>&1
 python YOND_SIDD.py --synthetic 40 2>&1 | grep -E "images on|steady|Iter" > $O/r05_eval_driver_synthetic40.txt
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --steps 2 --warmup 1 --frames-per-step 4 --no-cpu-baseline --no-extras --min-warmup-s 0"
+B="python3 $R/bench.py --full --steps 2 --warmup 1 --frames-per-step 4 --no-cpu-baseline --no-extras --min-warmup-s 0"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o t -- $B > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o f -- $B > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o w -- $B > /dev/null 2>&1

@@ -5,12 +5,12 @@
 set -x
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r06; mkdir -p $O
 cd $R
-python bench.py --steps 20 --warmup 5 2>$O/once.err | tail -1 > $O/r06_bench_once.json
-python bench.py --cfg 3 --steps 6 --warmup 2 2>/dev/null | tail -1 > $O/r06_bench_cfg3_sidd.json
-python bench.py --steps 10 --warmup 3 --mode iter --no-cpu-baseline 2>/dev/null | tail -1 > $O/r06_bench_iter.json
-python bench.py --steps 6 --warmup 2 --cfg 4 --no-cpu-baseline 2>/dev/null | tail -1 > $O/r06_bench_cfg4_unet_batch8.json
-python bench.py --steps 6 --warmup 2 --cfg 5 --no-cpu-baseline 2>/dev/null | tail -1 > $O/r06_bench_cfg5_fp16.json
-python bench.py --steps 6 --warmup 2 --precision fp32-mfma --no-cpu-baseline 2>/dev/null | tail -1 > $O/r06_bench_fp32_mfma.json
+python bench.py --full --steps 20 --warmup 5 2>$O/once.err | tail -1 > $O/r06_bench_once.json
+python bench.py --full --cfg 3 --steps 6 --warmup 2 2>/dev/null | tail -1 > $O/r06_bench_cfg3_sidd.json
+python bench.py --full --steps 10 --warmup 3 --mode iter --no-cpu-baseline 2>/dev/null | tail -1 > $O/r06_bench_iter.json
+python bench.py --full --steps 6 --warmup 2 --cfg 4 --no-cpu-baseline 2>/dev/null | tail -1 > $O/r06_bench_cfg4_unet_batch8.json
+python bench.py --full --steps 6 --warmup 2 --cfg 5 --no-cpu-baseline 2>/dev/null | tail -1 > $O/r06_bench_cfg5_fp16.json
+python bench.py --full --steps 6 --warmup 2 --precision fp32-mfma --no-cpu-baseline 2>/dev/null | tail -1 > $O/r06_bench_fp32_mfma.json
 python tools/stage_bench.py > $O/r06_stage_kernels.txt 2>&1
 python tools/layer_times.py > $O/r06_layer_times.txt 2>&1
 rm -f gpurun_out/lanes_ab.txt; bash tools/lanes_ab.sh "1:0 2:0" once; bash tools/lanes_ab.sh "1:0 2:0" cfg5 --cfg 5; cp gpurun_out/lanes_ab.txt $O/r06_lanes_ab.txt
@@ -24,8 +24,8 @@ cd /tmp && export TMPDIR=/tmp
 # (second session: the stream drivers run the network passes of consecutive frames on two lanes; a launch's wall duration then includes its wait for the other
 #  lane's workgroups, so the trace is taken twice -- the default command, and --lanes 1 for the kernels' own durations, which the roofline objects quote -- and the
 #  counter passes, which serialise the launches anyway, run on one lane)
-B="python3 $R/bench.py --steps 2 --warmup 1 --frames-per-step 4 --no-cpu-baseline --no-extras --min-warmup-s 0"
-B5="python3 $R/bench.py --cfg 5 --steps 2 --warmup 1 --frames-per-step 4 --no-cpu-baseline --no-extras --min-warmup-s 0"
+B="python3 $R/bench.py --full --steps 2 --warmup 1 --frames-per-step 4 --no-cpu-baseline --no-extras --min-warmup-s 0"
+B5="python3 $R/bench.py --full --cfg 5 --steps 2 --warmup 1 --frames-per-step 4 --no-cpu-baseline --no-extras --min-warmup-s 0"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o t -- $B > /dev/null 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace1 -o t -- $B --lanes 1 > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o f -- $B --lanes 1 > /dev/null 2>&1

@@ -4,10 +4,11 @@
 set -e
 out=gpurun_out/lanes_ab.txt
 variants="$1"; tag="$2"; shift; shift
+dir=$(dirname "$out")
 for rep in 1 2; do
   for v in $variants; do
     l=${v%%:*}; lp=${v##*:}
-    python bench.py --steps 4 --warmup 2 --no-extras --no-cpu-baseline --lanes $l --lane-pipelines $lp "$@" > gpurun_out/_lanes.json 2> gpurun_out/_lanes.err
+    python bench.py --full --steps 4 --warmup 2 --no-extras --no-cpu-baseline --lanes $l --lane-pipelines $lp "$@" > "$dir/_lanes.json" 2> "$dir/_lanes.err"
     python - "$tag" $v >> $out <<'PY'
 import json, sys
 d = json.loads(open("gpurun_out/_lanes.json").read().strip().splitlines()[-1])

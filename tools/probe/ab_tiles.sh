@@ -3,11 +3,12 @@
 # `python -m yond_public_amd.build`, copy yond_public_amd/libyond_hip.so to tools/probe/libyond_hip_prev.so (the commit before the tile-height
 # rule) / libyond_hip_prev2.so (the commit with the 8- / 16-row rule only), come back to HEAD and rebuild.
 cd $GRAFT_REPO_ROOT
+T=$(mktemp)
 one() { # lib cfg
-  YOND_HIP_LIB=$1 python bench.py --cfg $2 --steps 6 --warmup 2 --no-cpu-baseline --no-extras > gpurun_out/ab_tmp.json 2>/dev/null
+  YOND_HIP_LIB=$1 python bench.py --full --cfg $2 --steps 6 --warmup 2 --no-cpu-baseline --no-extras > $T 2>/dev/null
   python - <<PY
 import json
-d=json.loads(open("gpurun_out/ab_tmp.json").read().strip().split("\n")[-1])
+d=json.loads(open("$T").read().strip().split("\n")[-1])
 print("$1" or "new", "cfg$2", d["config"]["ms_per_frame"], d["conv_stack"]["ms_per_frame"], d["gfx_clock"]["in_kernel_mhz"])
 PY
 }
