@@ -565,6 +565,36 @@ int yond_adam_step_dev_f32(float* p, const float* g, float* m, float* v, size_t 
  * the chip holds under the load running beside it = out[0] / out[1] * 100 MHz. */
 int yond_clock_probe(double us, unsigned long long* out /* [2], device */, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * I1  sRGB crop -> raw training pair (img2raw.hip; memory bound, 3 or 6 B in + 8 B out per output)
+ * Replaces data_process/yond_datasets.py:277-334 and :483-548 (one item of RGB_Img2Raw_Dataset / DIV2K_Img2Raw_Dataset) with
+ * data_process/unprocess.py:80-148 (inverse_smoothstep, gamma_expansion, apply_ccm, safe_invert_gains, clamp, mosaic) and
+ * yond_datasets.py:15-19 (bayer_aug), for B crops of one shape in one launch.
+ *   crops      uint8 (dtype 0) or uint16 (dtype 1) [..][H][W][3] sRGB crops (device); crop b starts at element patches[b].offset
+ *              and needs offset + H*W*3 <= crops_len (a patch outside is written as NaN, nothing is read)
+ *   curve      float32 [256] (uint8) or [65536] (uint16) (device): the per-level transfer curve, gamma_expansion(inverse_smoothstep(
+ *              level / divisor)) evaluated by the host in the reference's float32 steps (uint8 curves go through LDS)
+ *   patches    YondImg2RawPatch [B] (device), one per crop
+ *   pattern    0..3: the Bayer rotation of every patch; -1: each patch's own `pattern` (mod 4), only for H == W
+ *   hr, lr     float32 [B][4][h'][w'], h' = H/2, w' = W/2 for an even rotation, swapped for an odd one; sigma (optional) float32 [B]
+ * Every output element is one pixel of the crop: rotated-mosaic site -> source pixel (Y, X) and channel (Y&1) + (X&1); its three
+ * channels go through the curve, out[c] = sum_j in[j] * rgb2cam[c][j], gray = (out0 + out1 + out2) / 3, mask = (max(gray - 0.9, 0)
+ * / 0.1)^2, one channel times max(mask + (1 - mask) * g, g), clamped to [0, 1] (float32; the 3-term CCM sums may differ from
+ * torch's BLAS in the last bit).  lr = hr + sigma * N(0, 1): Philox4x32-10 keyed by (key, slot), counter = the index of the
+ * 4-element group in the patch, Box-Muller -- a patch's noise depends on its key and slot only.  clip != 0 clamps lr to [0, 1].
+ * Refused (YOND_EINVAL, nothing launched): a null pointer, H or W odd or < 2, B < 1, a dtype other than 0 / 1, a pattern outside
+ * -1..3, pattern -1 with H != W. */
+typedef struct {
+    float rgb2cam[9];     /* row-major [c][j] (unprocess.py:7-47) */
+    float gain[3];        /* [1/red, 1, 1/blue] / rgb_gain in float32 (unprocess.py:112) */
+    float sigma;          /* noise standard deviation (already / 255) */
+    int pattern;          /* quarter turns of the mosaic (pattern -1 launches) */
+    unsigned key, slot;   /* noise stream */
+    long long offset;     /* first element of the crop in `crops` */
+} YondImg2RawPatch;       /* 72 bytes */
+int yond_img2raw_f32(const void* crops, size_t crops_len, int dtype, int H, int W, const float* curve, const YondImg2RawPatch* patches,
+                     int B, int pattern, int clip, float* hr, float* lr, float* sigma, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

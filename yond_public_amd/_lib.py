@@ -91,6 +91,7 @@ PROTOTYPES = {
     "yond_block_metrics_tiles": [i32, i32],
     "yond_block_metrics_f32": [vp, vp, i32, i32, i32, i32, vp, vp],
     "yond_clock_probe": [f64, vp, vp],
+    "yond_img2raw_f32": [vp, sz, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp],
     "yond_conv_wgrad_f32": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp],
     "yond_conv_wgrad_ws_f32": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp],
     "yond_conv_wgrad_ws_bytes": [i32, i32, i32, i32, i32, i32, i32, i32, i32],

@@ -11,11 +11,17 @@ backward, loss and Adam run on the HIP kernels (yond_public_amd/train.py), one p
 over RCCL in 25 MB buckets behind the backward pass (distributed.GradReducer) instead of torch DDP, every rank draws its own
 shard of the epoch's permutation (DistributedSampler's rule), and the evaluation forward is the inference engine.
 
-Data: the reference's training sets are sRGB crops pushed through `unprocess` + `mosaic` on the host (data_process/, outside
-SURVEY section 8).  Here a dataset directory holds patches that are ALREADY packed raw: `<root_dir>/<mode>[_<subname>]/*.npy`,
-each (4, h, w) or (h, w, 4) float in [0, 1]; the noise model on top is the reference's (yond_datasets.py:308-320:
-sigma log-uniform in [sigma_min, sigma_max] / 255 when training, the fixed `dst_eval.sigma` with a per-index seed otherwise;
-Bayer-pattern augmentation by rotating the mosaic, :296-303).  Without data the trainer draws seeded synthetic patches so that
+Data: a dataset directory (`<root_dir>/<mode>[_<subname>]/*.npy`; DIV2K_Img2Raw_Dataset also `<root_dir>/npy/<mode>`, the
+reference's layout) holds one of two kinds of patch.
+  - sRGB crops, (H, W, 3) uint8 / uint16, the reference's training sets: each batch is synthesised on the GPU in one launch
+    (yond_public_amd/img2raw.py, csrc/img2raw.hip) -- unprocess (random CCM, gains, gain mask), mosaic, Bayer-pattern rotation
+    and Gaussian noise, yond_datasets.py:277-334 -- from a device cache of the crops.  Metadata, pattern and sigma are drawn on
+    the host per (epoch, rank); evaluation item k gets the reference's metadata after setup_seed(k), pattern k % 4 and noise
+    key k, so every pass sees the same item.  The noise is Philox on the device, not NumPy's realisation.
+  - patches ALREADY packed raw, each (4, h, w) or (h, w, 4) float in [0, 1], with the reference's noise model on top on the host
+    (yond_datasets.py:308-320: sigma log-uniform in [sigma_min, sigma_max] / 255 when training, the fixed `dst_eval.sigma` with a
+    per-index seed otherwise; Bayer-pattern augmentation by rotating the mosaic, :296-303).
+A directory mixing the two is refused before the first step.  Without data the trainer draws seeded synthetic patches so that
 the loop can be exercised and timed.  Plots, FastISP previews and the consistency branch (`command: consistency`) are not built.
 """
 import argparse
@@ -31,6 +37,7 @@ import yaml
 
 from . import archs as _archs
 from . import distributed as D
+from . import img2raw as I
 from . import synthetic as S
 from . import train as T
 from .YOND_SIDD import log
@@ -76,10 +83,8 @@ class RGB_Img2Raw_Dataset:
     def __init__(self, args, synthetic=0):
         self.args = dict(args)
         self.mode = self.args['mode']
-        d = f"{self.args['root_dir']}/{self.mode}"
-        if self.mode == 'train':
-            d += f"_{self.args.get('subname', '')}" if 'subname' in self.args else ''
-        self.datapath = sorted(str(p) for p in Path(d).glob('*.npy')) if os.path.isdir(d) else []
+        d = self._data_dir()
+        self.datapath = _npy_files(d)
         self.names = [os.path.basename(p)[:-4] for p in self.datapath]
         self.synthetic = 0 if self.datapath else int(synthetic)
         if not self.datapath and not self.synthetic:
@@ -87,6 +92,12 @@ class RGB_Img2Raw_Dataset:
         self.buffer = [None] * len(self)
         self.h, self.w = self.args['H'] // 2, self.args['W'] // 2
         self.sigma = -1
+
+    def _data_dir(self):
+        d = f"{self.args['root_dir']}/{self.mode}"
+        if self.mode == 'train':
+            d += f"_{self.args.get('subname', '')}" if 'subname' in self.args else ''
+        return d
 
     def __len__(self):
         return len(self.datapath) or self.synthetic
@@ -97,7 +108,8 @@ class RGB_Img2Raw_Dataset:
                 a = np.load(self.datapath[idx])
                 if a.ndim != 3 or 4 not in (a.shape[0], a.shape[-1]):
                     raise ValueError(f"{self.datapath[idx]}: expected a packed raw patch (4, h, w) or (h, w, 4), got {a.shape} -- "
-                                     "sRGB crops need the reference's unprocess + mosaic first (not part of this build)")
+                                     "a directory of sRGB crops trains through AWGN_Trainer's device path (yond_public_amd/img2raw.py), "
+                                     "not through host items")
                 a = a.astype(np.float32)
                 self.buffer[idx] = a if a.shape[-1] == 4 else a.transpose(1, 2, 0)
             else:
@@ -130,7 +142,26 @@ class RGB_Img2Raw_Dataset:
         return data
 
 
-DIV2K_Img2Raw_Dataset = RGB_Img2Raw_Dataset                      # same item layout (yond_datasets.py:437-548), same noise model
+class DIV2K_Img2Raw_Dataset(RGB_Img2Raw_Dataset):
+    """yond_datasets.py:437-548: the same item layout and noise model.  When `<root_dir>/<mode>[_<subname>]` holds no .npy, the
+    reference's `<root_dir>/npy/<mode>` is used; sRGB crops are divided by 255 whatever their dtype (:469)."""
+
+    def _data_dir(self):
+        d = super()._data_dir()
+        ref = f"{self.args['root_dir']}/npy/{self.mode}"
+        return ref if not _npy_files(d) and _npy_files(ref) else d
+
+
+def _npy_files(d):
+    return sorted(str(p) for p in Path(d).glob('*.npy')) if os.path.isdir(d) else []
+
+
+def img2raw_source(ds, device):
+    """The device sRGB -> raw path (img2raw.Img2RawSource) of a dataset whose files are sRGB crops; None for packed raw or synthetic
+    patches.  A directory mixing both kinds raises here, before any step."""
+    if not ds.datapath or I.crop_kind(ds.datapath) != 'srgb':
+        return None
+    return I.Img2RawSource(ds.datapath, ds.args, device, div2k=isinstance(ds, DIV2K_Img2Raw_Dataset))
 
 
 def PSNR_Loss(low, high):
@@ -225,6 +256,7 @@ class AWGN_Trainer:
         self.print_model_log()
         if self.mode == 'train':
             self.dst_train = globals()[self.args['dst_train']['dataset']](self.args['dst_train'], self.parser.synthetic)
+            self.src_train = img2raw_source(self.dst_train, self.device)
         self.change_eval_dst('eval')
 
     # -- trainer_base.py:48-82 ------------------------------------------------------------------------------------------------
@@ -267,9 +299,12 @@ class AWGN_Trainer:
         self.dst = self.args[f'dst_{mode}']
         self.dstname = self.dst['dstname']
         self.dst_eval = globals()[self.dst['dataset']](self.dst, self.parser.synthetic)
+        self.src_eval = img2raw_source(self.dst_eval, self.device)
 
     # -- trainer_AWGN.py:347-368 -----------------------------------------------------------------------------------------------
     def preprocess(self, data, mode='train', preprocess=True):
+        if isinstance(data['hr'], torch.Tensor) and data['hr'].is_cuda:        # synthesised on the device, clipped there: as is
+            return data['lr'], data['hr'], data['sigma'].view(-1, 1, 1, 1)
         imgs_hr = torch.as_tensor(np.asarray(data['hr']), dtype=torch.float32).to(self.device)
         imgs_lr = torch.as_tensor(np.asarray(data['lr']), dtype=torch.float32).to(self.device)
         imgs_hr = imgs_hr.reshape(-1, *imgs_hr.shape[-3:])
@@ -280,6 +315,13 @@ class AWGN_Trainer:
         return imgs_lr, imgs_hr, sigma
 
     def _epoch_batches(self, epoch):
+        if self.src_train is not None:                 # sRGB crops: one img2raw launch per batch, noise slots numbered per epoch
+            gen, key = I.train_streams(epoch, self.rank)
+            for b, idx in enumerate(shard_batches(len(self.dst_train), self.hyper['batch_size'], epoch, self.rank, self.world)):
+                data = self.src_train.batch(idx, gen, key, b * len(idx))
+                data['name'] = [self.dst_train.names[int(i)] for i in idx]
+                yield data
+            return
         rng = np.random.default_rng([epoch, self.rank, 1997])
         for idx in shard_batches(len(self.dst_train), self.hyper['batch_size'], epoch, self.rank, self.world):
             items = [self.dst_train.__getitem__(int(i), rng) for i in idx]
@@ -333,9 +375,13 @@ class AWGN_Trainer:
                 metrics = pkl.load(f)
         guided = 'guided' in self.args['arch']
         for k in range(len(self.dst_eval)):
-            data = self.dst_eval[k]
-            imgs_lr, imgs_hr, sigma = self.preprocess({'lr': data['lr'][None], 'hr': data['hr'][None], 'sigma': data['sigma']},
-                                                      mode='eval', preprocess=False)
+            if self.src_eval is not None:
+                data = dict(self.src_eval.item(k, self.dst_eval.sigma), name=self.dst_eval.names[k])
+                imgs_lr, imgs_hr, sigma = self.preprocess(data, mode='eval', preprocess=False)
+            else:
+                data = self.dst_eval[k]
+                imgs_lr, imgs_hr, sigma = self.preprocess({'lr': data['lr'][None], 'hr': data['hr'][None], 'sigma': data['sigma']},
+                                                          mode='eval', preprocess=False)
             name = data['name'] + f'_sig{int(sigma.item() * 255)}'
             pad = imgs_lr.shape[-1] % 16 != 0                  # :220-225 (the reference calls a guided net without sigma there)
             x = torch.nn.functional.pad(imgs_lr, (4, 4, 4, 4), mode='reflect') if pad else imgs_lr
