@@ -595,6 +595,23 @@ typedef struct {
 int yond_img2raw_f32(const void* crops, size_t crops_len, int dtype, int H, int W, const float* curve, const YondImg2RawPatch* patches,
                      int B, int pattern, int clip, float* hr, float* lr, float* sigma, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * E1 / E2  edge layers of the noise-estimation network EstUnet (estnet.hip; archs/Unet.py:474-611, archs/comp.py:35-126).  The
+ * 3x3 layers between them, the pooling and the decoder's transposed 2x2 layers run on yond_conv2d_f32 / yond_maxpool2_f32.
+ *   yond_est_conv_in_f32  3x3 on ONE full-resolution plane x [N][H][W], zero padding 1, + bias, ReLU -> dst [N][H][W][Cout].
+ *                         w [Cout][9] and bias [Cout] on the device, zero-padded to Cout (a multiple of 32, <= 1024).
+ *                         64-bit element offsets.  HBM bound: 4 B in, 4 Cout B out per pixel.
+ *   yond_est_head_f32     1x1 from feat [N][H][W][Cin] (Cin a multiple of 4) to out_nc <= 4 channels (w [out_nc][Cin], bias [out_nc]),
+ *                         squared when sq != 0 ('var').  pge 0: out is the map [N][out_nc][H][W].  pge 1: out is the spatial mean
+ *                         [N][out_nc]; partial (device, yond_est_head_ws_bytes(N, out_nc) bytes = N * YOND_EST_HEAD_BLOCKS * out_nc
+ *                         doubles) holds per-workgroup float64 sums, added in a fixed order by a second launch: the same input gives
+ *                         the same bits, no atomics. */
+#define YOND_EST_HEAD_BLOCKS 512
+int yond_est_conv_in_f32(const float* x, int N, int H, int W, int Cout, const float* w, const float* bias, float* dst, void* stream);
+int yond_est_head_f32(const float* feat, int N, int H, int W, int Cin, const float* w, const float* bias, int out_nc, int sq, int pge,
+                      float* out, double* partial, void* stream);
+size_t yond_est_head_ws_bytes(int N, int out_nc);
+
 #ifdef __cplusplus
 }
 #endif

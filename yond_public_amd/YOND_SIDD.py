@@ -91,6 +91,34 @@ class NpySIDD:
         return d
 
 
+def load_estimators(args, device, logfile=None, beta=(4.0 / 959, 6.0 / 959)):
+    """YOND_SIDD.py:187-196: every top-level runfile key that contains 'est_' is one network, built by name from
+    yond_public_amd.archs with the section as its arguments and loaded from section['weights'].  A missing weights file is
+    logged and replaced by deterministic estimation weights (synthetic.estimation_state_dict: conv_final's bias = beta, the
+    (beta1, sqrt(beta2)) of the synthetic stand-in frames), as the denoiser's missing checkpoint is.  Returns (sections, networks)."""
+    est_args = {key: args[key] for key in args if 'est_' in key}
+    est_net = {}
+    for name, sec in est_args.items():
+        cls = getattr(_archs, str(sec.get('name')), None)
+        if cls is None:
+            raise SystemExit(f"runfile section {name}: no network {sec.get('name')!r} in yond_public_amd.archs")
+        net = cls(sec)
+        path = sec.get('weights')
+        if path and os.path.exists(path):
+            # load_weights(by_name=False) (utils/utils.py:160-204): the checkpoint's entries over the model's own state_dict, so a
+            # checkpoint without some of the model's keys (noiseSTD, say) loads; a key the model does not have still raises
+            state = net.state_dict()
+            state.update(torch.load(path, map_location='cpu'))
+            net.load_state_dict(state)
+            src = path
+        else:
+            net.load_state_dict(S.estimation_state_dict(net, beta))
+            src = f"{path} not found -> synthetic estimation weights"
+        est_net[name] = net.to(device).eval()
+        log(f'Estimator {name}:\t{sec.get("name")} ({src})', logfile, notime=True)
+    return est_args, est_net
+
+
 class YOND_SIDD:
     def __init__(self, args=None):
         self.parser = YONDParser().parse(args)
@@ -124,6 +152,7 @@ class YOND_SIDD:
             model_path = None                      # no checkpoint: a deterministic weak denoiser (both rounds run)
             self.net.load_state_dict(S.denoising_state_dict(self.net, 0))
         self.net = self.net.to(self.device).eval()
+        self.est_args, self.est_net = load_estimators(self.args, self.device, self.logfile if self.rank == 0 else None)
         # the 2-D bias LUT when its blob is present (YOND_SIDD.py:171), else get_bias per image
         self.biaslut = P.BiasLUT() if os.path.exists('checkpoints/bias_lut_2d.npy') else None
         if self.rank == 0:
@@ -156,14 +185,18 @@ class YOND_SIDD:
         return P.VST_Denoiser(lr_raw, p, self.net, self.arch, bias_corr, bias_func, self.pipe.get('vst_type', 'exact'),
                               device=self.device, biaslut=self.biaslut)
 
+    def _est(self, data, params):
+        """What IterDenoise's estimate may read: the dataset tree and image (file estimates), the est_* sections and their networks."""
+        return {'root_dir': (getattr(self, 'dst', None) or {}).get('root_dir'), 'img_id': params.get('img_id'), 'name': data.get('name'),
+                'est_net': (getattr(self, 'est_net', None) or {}).get('est_net'), 'est_args': getattr(self, 'est_args', None) or {}}
+
     def IterDenoise(self, data, params):
         # data['lr'] is the [32][256][256] stack; pipeline.IterDenoise concatenates it for the estimate (:315) and, with
         # pipe['full_dn'], for the denoiser (:388); the collaborative estimate re-tiles per block (SIDD_256, :431)
         res = P.IterDenoise(data['lr'], self.net, self.arch, self.pipe, lr_full=data.get('lr_full'), p=params['p'],
                             device=self.device, log=(lambda s: log(s, self.logfile)) if self.parser.verbose else None,
                             biaslut=self.biaslut,
-                            est={'root_dir': (getattr(self, 'dst', None) or {}).get('root_dir'), 'img_id': params.get('img_id'),
-                                 'name': data.get('name')})
+                            est=self._est(data, params))
         cat = lambda a: torch.cat(list(a), dim=-1) if isinstance(a, torch.Tensor) else np.concatenate(a, axis=-1)   # (:480-481)
         res['lr_raw'] = cat(data['lr'])
         res['hr_raw'] = cat(data['hr']) if data.get('hr') is not None else None
@@ -176,8 +209,7 @@ class YOND_SIDD:
         (16 x 16 and 8 x 8 pixels) far too small for the chip."""
         ress = P.IterDenoiseGroup([(d['lr'], d.get('lr_full')) for d in datas], self.net, self.arch, self.pipe, ps=[q['p'] for q in params_list],
                                   device=self.device, log=(lambda s: log(s, self.logfile)) if self.parser.verbose else None, biaslut=self.biaslut,
-                                  ests=[{'root_dir': (getattr(self, 'dst', None) or {}).get('root_dir'), 'img_id': q.get('img_id'), 'name': d.get('name')}
-                                        for d, q in zip(datas, params_list)])
+                                  ests=[self._est(d, q) for d, q in zip(datas, params_list)])
         cat = lambda a: torch.cat(list(a), dim=-1) if isinstance(a, torch.Tensor) else np.concatenate(a, axis=-1)   # (:480-481)
         for res, d in zip(ress, datas):
             res['lr_raw'] = cat(d['lr'])

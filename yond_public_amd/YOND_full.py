@@ -26,7 +26,7 @@ from . import data as _data
 from . import distributed as D
 from . import pipeline as P
 from . import synthetic as S
-from .YOND_SIDD import YONDParser, log
+from .YOND_SIDD import YONDParser, load_estimators, log
 
 STREAM_EVAL = True                 # eval(): frames through pipeline.denoise_stream (False: IterDenoise one frame at a time, synchronised after every frame)
 
@@ -81,6 +81,7 @@ class YOND_Full:
             model_path = None
             self.net.load_state_dict(S.denoising_state_dict(self.net, 0))
         self.net = self.net.to(self.device).eval()
+        self.est_args, self.est_net = load_estimators(self.args, self.device, self.logfile if self.rank == 0 else None)
         self.biaslut = P.BiasLUT() if os.path.exists('checkpoints/bias_lut_2d.npy') else None
         if self.rank == 0:
             log(f'Method Name:\t{self.method_name}', self.logfile, notime=True)
@@ -102,7 +103,8 @@ class YOND_Full:
 
     def IterDenoise(self, data, params):
         return P.IterDenoise(data['lr'], self.net, self.arch, self.pipe, p=params['p'], device=self.device,
-                             log=(lambda s: log(s, self.logfile)) if self.parser.verbose else None, biaslut=self.biaslut)
+                             log=(lambda s: log(s, self.logfile)) if self.parser.verbose else None, biaslut=self.biaslut,
+                             est={'est_net': self.est_net.get('est_net'), 'est_args': self.est_args})
 
     def _sweeps(self):
         """(label, switch) per evaluated subset: ratio_list x cam_list as the runfile gives them."""

@@ -92,6 +92,9 @@ PROTOTYPES = {
     "yond_block_metrics_f32": [vp, vp, i32, i32, i32, i32, vp, vp],
     "yond_clock_probe": [f64, vp, vp],
     "yond_img2raw_f32": [vp, sz, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp],
+    "yond_est_conv_in_f32": [vp, i32, i32, i32, i32, vp, vp, vp, vp],
+    "yond_est_head_f32": [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp],
+    "yond_est_head_ws_bytes": [i32, i32],
     "yond_conv_wgrad_f32": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp],
     "yond_conv_wgrad_ws_f32": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp],
     "yond_conv_wgrad_ws_bytes": [i32, i32, i32, i32, i32, i32, i32, i32, i32],
@@ -136,7 +139,8 @@ EXPERIMENT_PROTOTYPES = {
     "yond_pack_block0_weight_f32": [vp, i32, i32, vp],
 }
 _SIZE_T_RET = {"yond_select_ws_bytes", "yond_nle_ws_bytes", "yond_lut_ws_bytes", "yond_bias_lut_big_scratch", "yond_bias_points_scratch",
-               "yond_conv_wgrad_ws_bytes", "yond_conv_wgrad_split_ws_bytes"}
+               "yond_conv_wgrad_ws_bytes", "yond_conv_wgrad_split_ws_bytes",
+               "yond_est_head_ws_bytes"}
 
 
 class YondHipError(RuntimeError):

@@ -1,7 +1,8 @@
 """`from yond_public_amd.archs import *` mirrors `from archs import *` (YOND_SIDD.py:7) for the
-hot-path denoisers; classes are resolved by name from the runfile's arch['name']."""
+hot-path denoisers and the estimation network of the `est_*` sections; classes are resolved by name from the runfile's arch['name']."""
 import torch.nn as nn
 
+from .est import EstUnet
 from .unet import GuidedResUnet, SNRnet, UNetSeeInDark
 
 
@@ -16,4 +17,4 @@ def initialize_weights(net):
             m.weight.data.normal_(0.0, 0.02)
 
 
-__all__ = ["GuidedResUnet", "SNRnet", "UNetSeeInDark", "initialize_weights"]
+__all__ = ["GuidedResUnet", "SNRnet", "UNetSeeInDark", "EstUnet", "initialize_weights"]

@@ -227,14 +227,7 @@ class DenoiserPlan:
     """Packs a module's parameters once and runs forwards on NHWC4 device tensors."""
 
     def __init__(self, module, device):
-        self.lib = L.load()
-        self.dev = torch.device(device)
-        self.prof = None                           # list -> record (kernel tag, flops, start, end) HIP events per conv launch
-        self.status = torch.zeros(12, dtype=torch.int32, device=self.dev)    # range-guard words of the half-precision paths (0-2: pipeline wrappers, 3: the
-                                                                             # plugin surface, 4-11: the two-stream 'iter' driver's ring)
-        self.status_slot = 0
-        self.strict = False                        # True: every convolution on the fp32-input MFMA kernels (guard fallback)
-        self.precision = getattr(module, 'precision', 'fp32')      # 'fp16': MFMA convolutions on the fp16 matrix path (cfg 5)
+        self._init_launcher(device, getattr(module, 'precision', 'fp32'))
         self.kind = type(module).__name__          # GuidedResUnet | SNRnet | UNetSeeInDark
         self.res = bool(module.res)
         self.norm = bool(module.norm)
@@ -302,6 +295,17 @@ class DenoiserPlan:
                 self.convs[f'conv{i}_2'] = _PackedConv(dev, sd[f'conv{i}_2.weight'], sd[f'conv{i}_2.bias'], 3, 1, [c])
             self.w_out = self._pad_out_w(sd['conv10_1.weight'])
             self.b_out = sd['conv10_1.bias'].to(dev, torch.float32).contiguous()
+
+    def _init_launcher(self, device, precision):
+        """The state `_conv`, `_new_sp` and the range guard read (shared with estnet.EstimatorPlan)."""
+        self.lib = L.load()
+        self.dev = torch.device(device)
+        self.prof = None                           # list -> record (kernel tag, flops, start, end) HIP events per conv launch
+        self.status = torch.zeros(12, dtype=torch.int32, device=self.dev)    # range-guard words of the half-precision paths (0-2: pipeline wrappers, 3: the
+                                                                             # plugin surface, 4-11: the two-stream 'iter' driver's ring)
+        self.status_slot = 0
+        self.strict = False                        # True: every convolution on the fp32-input MFMA kernels (guard fallback)
+        self.precision = precision                 # 'fp16': MFMA convolutions on the fp16 matrix path (cfg 5)
 
     # -- packing helpers -------------------------------------------------------------------
     def _pack_conv_in(self, w, b):

@@ -1149,7 +1149,8 @@ def file_estimate(pipe, est=None):
         foi / liu       SIDD_Validation_Raw/{FoiEst,LiuEst}_fullPict.mat, variable 'return_params' (:324-327)
         zou             SIDD_Validation_Raw/Zou_fullPict.npy (:328-329)
         pge             SIDD_Validation_Raw/PGE_fullPict.npy; its second column is a standard deviation (:330-337)
-    Returns None for the est_types that compute ('simple', 'manual').  Host-side file reads: nothing here touches the GPU."""
+    Returns None for the est_types that compute ('simple', 'manual', 'ours'; 'pge' with est['est_net'] is IterDenoise's).  Host-side
+    file reads: nothing here touches the GPU."""
     est = est or {}
     est_type = str(pipe.get('est_type', 'simple'))
 
@@ -1179,10 +1180,92 @@ def file_estimate(pipe, est=None):
         return (r[0], r[1])
     if 'pge' in est_type:
         if est.get('est_net') is not None:
-            raise NotImplementedError("est_type 'pge' with an estimation network (YOND_SIDD.py:333-335) is not built: the file form only")
+            raise NotImplementedError("est_type 'pge' with an estimation network (YOND_SIDD.py:333-335) is not a file lookup: "
+                                      "IterDenoise runs the network (net_estimate)")
         r = np.array(np.load(os.path.join(raw_dir(), 'PGE_fullPict.npy'))[need('img_id')], dtype=np.float64)
         return (r[0], r[1] ** 2)
     return None
+
+
+def net_estimate(est_net, x):
+    """(beta1, beta2) per frame from the estimation network (YOND_SIDD.py:333-336, 362-365): x [N][H][W] device frames -> the float32
+    host array [N][out_nc] with column 1 squared (the network regresses a standard deviation), as the reference's
+    `reg.detach().cpu().numpy(); reg[1] = reg[1] ** 2`.  One forward, one read back (the range guard's status word with it)."""
+    if not hasattr(est_net, 'plan'):
+        raise L.YondHipError(f"est_net must be an EstUnet of yond_public_amd.archs, got {type(est_net).__name__}")
+    with torch.no_grad():
+        r = est_net.plan(x.device).forward_checked(x.contiguous())
+    if r.dim() != 2 or r.shape[1] < 2:
+        raise L.YondHipError(f"the estimation network must regress per-image (beta1, sqrt(beta2)) (pge True, out_nc >= 2), got {tuple(r.shape)}")
+    r = r.cpu().numpy()
+    r[:, 1] = r[:, 1] ** 2
+    return r
+
+
+def _section_k(est, name):
+    """k of the runfile's est_self / est_collab section (est_type 'ours', YOND_SIDD.py:343, 426)."""
+    sec = ((est or {}).get('est_args') or {}).get(name)
+    if not sec or 'k' not in sec:
+        raise NotImplementedError(f"est_type 'ours' reads k from the runfile's {name} section (NeuralNLF): IterDenoise needs "
+                                  f"est={{'est_args': {{'{name}': {{'k': ...}}}}}}")
+    return int(sec['k'])
+
+
+def check_estimate_config(pipe, est=None):
+    """Configurations the reference cannot run, refused before any GPU work."""
+    est_type = str(pipe.get('est_type', 'simple'))
+    if not pipe.get('full_est', True) and 'pge' in est_type and pipe.get('iter', 'iter') == 'iter':
+        raise L.YondHipError("est_type 'pge' with full_est False estimates per block ([32][2]); round 2 ('iter') compares that array "
+                             "with 0 (YOND_SIDD.py:438) and fails in the reference: use iter 'once'")
+
+
+def pge_block_table(est):
+    """YOND_SIDD.py:360, 366: the per-block estimates of image est['img_id'] from SIDD_Validation_Raw/PGE.npy ([32][2], column 1 a
+    standard deviation, squared here).  Host-side file read."""
+    if est.get('root_dir') is None or est.get('img_id') is None:
+        raise L.YondHipError("est_type 'pge' without est_net reads SIDD_Validation_Raw/PGE.npy: IterDenoise needs est={'root_dir', 'img_id'}")
+    reg = np.array(np.load(os.path.join(str(est['root_dir']), 'SIDD_Validation_Raw', 'PGE.npy'))[est['img_id']])
+    reg[:, 1] = reg[:, 1] ** 2
+    return reg
+
+
+def _iter_denoise_pge_blocks(lr, blocks, lr_cat, net, arch, pipe, p, bias_corr, biaslut, est, rot_k_, log):
+    """YOND_SIDD.py:358-408 with est_type 'pge' and full_est False: one estimate per block -- a batch-32 forward of the estimation network,
+    or SIDD_Validation_Raw/PGE.npy -- the shared bias LUT from the blocks' mean (beta1, beta2), and with est_type == 'pge' every block
+    denoised with its own (gain, sigma); round 1 only."""
+    est = est or {}
+    scale = p['wp'] - p['bl']
+    est_type = str(pipe.get('est_type', 'simple'))
+    if est.get('est_net') is not None:
+        reg = net_estimate(est['est_net'], blocks)                                     # :362-364
+    else:
+        reg = pge_block_table(est)
+    p['gain'], p['sigma'] = reg[:, 0].mean() * scale, np.sqrt(max(reg[:, 1].mean(), 0)) * scale                          # :380-381
+    if log:
+        log(f"Self Est (mean): K={p['gain']:.4f}, b={p['sigma']:.4f} (beta1={reg[:, 0].mean():.3e}, beta2={reg[:, 1].mean():.3e})")
+    params = [(p['gain'], p['sigma'])]
+    vst_type = pipe.get('vst_type', 'exact')
+    if pipe.get('full_dn', False):                                                     # :387-389: the mean estimate, no shared LUT
+        raw_dn = VST_Denoiser(lr_cat, p, net, arch, bias_corr, None, vst_type, clip01=True, biaslut=biaslut)
+        return dict(raw_dns=[raw_dn], regs=[reg], params=params)
+    bias_func = None
+    if bias_corr is not None and biaslut is None:                                      # :392-397: built once, from the mean p
+        lr_max = np.float32(_frame_max(lr).item())
+        bias_func = get_bias(lr_max * scale, p['sigma'], p['gain'], device=lr.device)
+    if est_type == 'pge':                                                              # :399-400: every block its own p
+        ps = []
+        for num in range(blocks.shape[0]):
+            q = dict(p)
+            q['gain'], q['sigma'] = reg[num, 0] * scale, np.sqrt(max(reg[num, 1], 0)) * scale
+            ps.append(q)
+    else:
+        ps = [dict(p) for _ in range(blocks.shape[0])]
+    blk = rot90(blocks, rot_k_) if rot_k_ else blocks
+    # with the 2-D table every block takes its own row (bias_func None); else the shared LUT of the mean p
+    outs = VST_Denoiser(blk, ps, net, arch, bias_corr, [bias_func] * blk.shape[0], vst_type, clip01=True, biaslut=biaslut)
+    if rot_k_:
+        outs = rot90(outs, 4 - rot_k_)
+    return dict(raw_dns=[torch.cat(list(outs), dim=-1).contiguous()], regs=[reg], params=params)
 
 
 def IterDenoise(lr_raw, net, arch, pipe, lr_full=None, p=None, device=None, log=None, biaslut=None, est=None):
@@ -1192,7 +1275,9 @@ def IterDenoise(lr_raw, net, arch, pipe, lr_full=None, p=None, device=None, log=
     frame [H][W] (needs pipe['full_dn']).  The collaborative estimate re-tiles into 32 vertical tiles (SIDD_256, which :431
     hard-codes) wherever the reference's split can run (packed width divisible by 32); pipe['collab_sidd256'] overrides.  Returns dict(raw_dns, regs, params) with
     device tensors in raw_dns (each [H][W], for SIDD the 256 x 8192 concatenation as in the reference).
-    est: {'root_dir', 'img_id', 'name'} for the est_types that read round 1's estimate from files (file_estimate)."""
+    est: {'root_dir', 'img_id', 'name'} for the est_types that read round 1's estimate from files (file_estimate); 'est_net' (an
+    archs.EstUnet) for est_type 'pge' with the runfile's est_net section; 'est_args' (the runfile's est_* sections) for 'ours'."""
+    check_estimate_config(pipe, est)
     p = dict(p or default_params())
     k = pipe.get('k', 29)
     bias_corr = pipe.get('bias_corr', 'pre')
@@ -1236,7 +1321,9 @@ def IterDenoise(lr_raw, net, arch, pipe, lr_full=None, p=None, device=None, log=
         lr_cat = lr
     if not pipe.get('full_est', True):         # :358-381: no estimate at all -- every block through Simple_Denoiser
         if 'pge' in str(pipe.get('est_type', '')):
-            raise NotImplementedError("est_type 'pge' reads precomputed estimates from the dataset directory (:359-366)")
+            if not stack:
+                raise L.YondHipError("est_type 'pge' with full_est False estimates per block: it needs the SIDD stack [32][256][256]")
+            return _iter_denoise_pge_blocks(lr, blocks, lr_cat, net, arch, pipe, p, bias_corr, biaslut, est, rot_k_, log)
         if not stack:
             raise L.YondHipError("the Simple_Denoiser branch works on the SIDD stack [32][256][256]")
         outs = [Simple_Denoiser(blocks[num], net) for num in range(32)]                # :369-370
@@ -1245,13 +1332,19 @@ def IterDenoise(lr_raw, net, arch, pipe, lr_full=None, p=None, device=None, log=
     # lr.max() for the bias LUT grid: the estimator's first kernel collects it when it reads the same frame; else a
     # reduction queued ahead of the NLE and read after the NLE's own host sync
     est_type = str(pipe.get('est_type', 'simple'))
-    if 'ours' in est_type and 'cal_est' not in pipe:                                   # :342-348: NeuralNLF, a second network
-        raise NotImplementedError(f"est_type {est_type!r}: the reference estimates with a second network (NeuralNLF, YOND_SIDD.py:342-348); "
-                                  "this build estimates with 'simple', takes 'manual' or reads the other methods' files")
-    looked_up = file_estimate(pipe, est)                                               # :316-337 (cal_est first, as the reference's chain)
+    with_net = 'pge' in est_type and 'cal_est' not in pipe and (est or {}).get('est_net') is not None
+    looked_up = None if with_net else file_estimate(pipe, est)                         # :316-337 (cal_est first, as the reference's chain)
     if looked_up is not None:
         reg = (np.float64(looked_up[0]), np.float64(looked_up[1]))
         lr_max_dev, nle_info = _frame_max(lr_cat), {}
+    elif with_net:                                                                     # :333-336: the network on the concatenated frame
+        r = net_estimate(est['est_net'], lr_cat[None])[0]
+        reg = (np.float64(r[0]), np.float64(r[1]))
+        lr_max_dev, nle_info = _frame_max(lr_cat), {}
+    elif 'ours' in est_type:                                                           # :342-348: NeuralNLF = SimpleNLF with est_self's k
+        k = _section_k(est, 'est_self')                                                # (the network it is handed is never read)
+        lr_max_dev = _frame_max(lr_cat) if lr_full is not None else None
+        reg, nle_info = SimpleNLF(raw4est, k=k, setting={'mode': 'self'}, full=True)
     elif 'simple' in est_type:
         lr_max_dev = _frame_max(lr_cat) if lr_full is not None else None
         reg, nle_info = SimpleNLF(raw4est, k=k, setting={'mode': 'self'}, full=True)   # :341
@@ -1301,6 +1394,8 @@ def IterDenoise(lr_raw, net, arch, pipe, lr_full=None, p=None, device=None, log=
             # width divides by 32 (pinned by tests/golden/iter_full.npz); for other widths (3000 x 4000: 2000 / 32) the
             # reference's split raises, and the estimate is taken without re-tiling.  pipe['collab_sidd256'] overrides.
             can_tile = (lr_cat.shape[-1] // 2) % 32 == 0
+            if 'ours' in est_type:                                                     # :425-429: NeuralNLF = SimpleNLF with est_collab's k
+                k = _section_k(est, 'est_collab')
             reg = SimpleNLF(lr_cat, raw_dn, k=k,
                             setting={'mode': 'collab', 'SIDD_256': bool(pipe.get('collab_sidd256', sidd or stack or can_tile))})   # :431
             if reg[1] < 0:                                                             # :438-440

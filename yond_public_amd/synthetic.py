@@ -111,3 +111,16 @@ def denoising_state_dict(net, seed=0, eps=0.004):
                 w[c, cout + c, 0, 0] += 1.0                                # cat([up, skip]): identity on the skip half
     last_layer('conv10')
     return sd
+
+
+def estimation_state_dict(net, beta, seed=0):
+    """Deterministic weights for an EstUnet without a checkpoint: the procedural weights with conv_final's weights times 1e-3 and
+    its bias set to beta (e.g. (beta1, sqrt(beta2)) of the frame): the network's mean output is then close to a plausible noise
+    level, so that IterDenoise runs both rounds on it."""
+    sd = procedural_state_dict(net, seed)
+    sd['conv_final.weight'] = sd['conv_final.weight'] * 1e-3
+    b = torch.zeros_like(sd['conv_final.bias'])
+    beta = [float(v) for v in beta][:b.numel()]
+    b[:len(beta)] = torch.tensor(beta, dtype=b.dtype)
+    sd['conv_final.bias'] = b
+    return sd
