@@ -664,6 +664,37 @@ def procedural_state_dict(arch, seed=0, gain=1.0):
     return sd
 
 
+def stress_state_dict(arch, seed=0, gains=None):
+    """Checkpoint-like weights (tests/golden/net_stress.npz): every convolution of the data path -- 3x3, stride 2, transposed, short cut,
+    input and output layers -- draws Student-t (nu = 3) / sqrt(fan-in) weights, each output channel scaled by 10^U(-2, 2), eight input
+    channels x 1e3 in the odd output channels (tests/split_model.stress_weights has the reason for 'odd'); the FiLM layers and the biases
+    keep procedural_state_dict's law.  `gains` {weight key: factor} rescales a layer's weight and bias: tools/gen_golden_stress.py finds
+    them from the reference's own forward so that its activations stay inside fp16's range, and stores them in the fixture."""
+    import zlib
+    sd = procedural_state_dict(arch, seed)
+    for key in sorted(sd):
+        if not key.endswith('.weight') or any(f in key for f in ('.gamma.', '.beta.', '.sfm1.', '.sfm2.')):
+            continue
+        rng = np.random.default_rng([seed, zlib.crc32(key.encode())])
+        shape = tuple(sd[key].shape)
+        tr = 'upv' in key                                # ConvTranspose2d: [in][out][2][2]
+        co, ci = (shape[1], shape[0]) if tr else (shape[0], shape[1])
+        fan_in = ci if tr else ci * shape[2] * shape[3]
+        w = rng.standard_t(3, (co, ci, shape[2], shape[3])) / math.sqrt(fan_in)
+        w *= 10.0 ** rng.uniform(-2, 2, (co, 1, 1, 1))
+        if ci >= 16:
+            w[1::2, rng.choice(ci, 8, replace=False)] *= 1e3
+        if tr:
+            w = w.transpose(1, 0, 2, 3)
+        sd[key] = torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32))
+    for key, g in (gains or {}).items():
+        sd[key] = sd[key] * float(g)
+        bkey = key[:-len('weight')] + 'bias'
+        if bkey in sd:
+            sd[bkey] = sd[bkey] * float(g)
+    return sd
+
+
 def denoising_state_dict(arch, seed=0, eps=0.004):
     """Deterministic weights that make the network a (weak but real) DENOISER, so that round 2 of IterDenoise --
     the collaborative estimate from (noisy, denoised) -- is well posed and the reference's guards let it run

@@ -3,6 +3,7 @@ the reference itself (oracle/gen_golden.py).  These pin the oracle; see its head
 unpinned boundary (cv2.blur)."""
 import hashlib
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -406,3 +407,22 @@ def test_oracle_full_cfg2_round1(golden):
     np.testing.assert_allclose(res['regs'][0], g["a_reg0"], rtol=1e-5)
     for got, tag in zip(full_crops(res['raw_dns'][0]), ("a", "b", "c", "sub")):
         np.testing.assert_allclose(got, g[f"a_dn0_{tag}"], rtol=0, atol=2e-5)
+
+
+def test_stress_fixture_is_reproduced_from_its_seed_and_gains(golden):
+    """tests/golden/net_stress.npz stores outputs, seeds and per-layer gains only: oracle.stress_state_dict and the generator's input law
+    must give back the reference's float32 output (the oracle restates the reference's forward: same torch ops, same bits up to the
+    order of independent roundings) -- the tripping weights included."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    import gen_golden_stress as G
+    g = golden("net_stress")
+    for case in ("gru32_hi", "gru32_trip"):
+        ci = [c[0] for c in G.CASES].index(case)
+        _, aname, shape, sigma, trip = G.CASES[ci]
+        x = G.stress_input(shape, ci)
+        gains = dict(zip([str(k) for k in g[f"gain_keys_{aname}"]], g[f"gains_{aname}"]))
+        if trip:
+            gains.update(zip([str(k) for k in g["trip_keys"]], g["trip_gains"]))
+        y = O.net_forward(G.ARCHS[aname], O.stress_state_dict(G.ARCHS[aname], G.SEED, gains), x, G.stress_t(x, sigma))
+        for i, crop in enumerate(G.crops(y)):
+            assert float(np.abs(crop.numpy() - g[f"y{i}_{case}"]).max()) <= 1e-6 * max(1.0, float(g[f"y_absmax_{case}"]))

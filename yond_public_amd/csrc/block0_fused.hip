@@ -119,7 +119,7 @@ __global__ __launch_bounds__(512) void block0_fused_kernel(const YondBlock0Desc 
     // consecutive pixels of a group: contiguous along a region row in planes of 4, conflict-free 8-byte LDS writes); item 8: pixel
     // 512 + (tid & 63), group tid >> 6 (the region has 576 = 512 + 64 pixels)
     const int pixA = tid, pixB = 512 + (tid & 63), gB = tid >> 6;
-    float amax = 0.0f;
+    YondRange amax;
     f32x4 vin[B0_NIN];
     bool okA = false, okB = false;
     auto load_input = [&](const B0Tile& T) {
@@ -152,7 +152,7 @@ __global__ __launch_bounds__(512) void block0_fused_kernel(const YondBlock0Desc 
         f32x4 v;
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = ok ? b0_silu(vin[k][e]) : 0.0f;          // conv zero padding
-        amax = fmaxf(amax, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
+        amax.add(v);
         const b0_f16x4 h = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
         const b0_f16x4 l = {(_Float16)((v[0] - (float)h[0]) * 2048.0f), (_Float16)((v[1] - (float)h[1]) * 2048.0f),
                             (_Float16)((v[2] - (float)h[2]) * 2048.0f), (_Float16)((v[3] - (float)h[3]) * 2048.0f)};
@@ -218,7 +218,7 @@ __global__ __launch_bounds__(512) void block0_fused_kernel(const YondBlock0Desc 
                 y = b0_silu(fmaf(y, es[e], et[e]));
                 v[e] = ok ? y : 0.0f;                                  // outside the image: conv2's zero padding
             }
-            amax = fmaxf(amax, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
+            amax.add(v);
             const b0_f16x4 h = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
             const b0_f16x4 l = {(_Float16)((v[0] - (float)h[0]) * 2048.0f), (_Float16)((v[1] - (float)h[1]) * 2048.0f),
                                 (_Float16)((v[2] - (float)h[2]) * 2048.0f), (_Float16)((v[3] - (float)h[3]) * 2048.0f)};
@@ -433,7 +433,7 @@ __global__ __launch_bounds__(512) void block0_fused_kernel(const YondBlock0Desc 
                 } else {
 #pragma unroll
                     for (int mb = 0; mb < 2; ++mb) {
-                        amax = fmaxf(amax, fmaxf(fmaxf(fabsf(v[mb][0]), fabsf(v[mb][1])), fmaxf(fabsf(v[mb][2]), fabsf(v[mb][3]))));
+                        amax.add(v[mb]);
                         const b0_f16x4 h = {(_Float16)v[mb][0], (_Float16)v[mb][1], (_Float16)v[mb][2], (_Float16)v[mb][3]};
                         const b0_f16x4 l = {(_Float16)((v[mb][0] - (float)h[0]) * 2048.0f), (_Float16)((v[mb][1] - (float)h[1]) * 2048.0f),
                                             (_Float16)((v[mb][2] - (float)h[2]) * 2048.0f), (_Float16)((v[mb][3] - (float)h[3]) * 2048.0f)};
@@ -455,7 +455,7 @@ __global__ __launch_bounds__(512) void block0_fused_kernel(const YondBlock0Desc 
         T = Tn;
         ++dbg_tile;
     }
-    if (d.status && !(amax <= 65504.0f)) atomicOr(d.status, 1);      // a staged value left fp16's range (or is NaN: the comparison fails)
+    if (d.status && !amax.at_most(65504.0f)) atomicOr(d.status, 1);      // a staged value left fp16's range or is NaN (YondRange orders NaN patterns above every limit)
 }
 
 }  // namespace

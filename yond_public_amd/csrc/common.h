@@ -26,6 +26,27 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
         if (e__ != hipSuccess) return (int)e__;      \
     } while (0)
 
+// Range guard of the half-precision operand paths: the largest magnitude a thread has staged or stored as halves, kept as BIT PATTERNS so
+// that a NaN counts (fmaxf -- v_max_f32 -- returns the other operand when one is NaN: a float maximum never sees it).  Non-negative floats
+// order as signed integers, floats with the sign bit as unsigned ones (above every non-negative pattern, larger magnitude = larger pattern);
+// +-inf and every NaN lie above any finite limit's pattern.  Two integer max3 per accumulator and four values.
+struct YondRange {
+    int pos = 0;
+    unsigned neg = 0;
+    __device__ __forceinline__ void add(const f32x4& v) {
+        const int b0 = __float_as_int(v[0]), b1 = __float_as_int(v[1]), b2 = __float_as_int(v[2]), b3 = __float_as_int(v[3]);
+        pos = max(max(max(pos, b0), b1), max(b2, b3));
+        neg = max(max(max(neg, (unsigned)b0), (unsigned)b1), max((unsigned)b2, (unsigned)b3));
+    }
+    // every value seen so far is finite, not NaN, and |v| <= limit (at_most) / |v| < limit (below); limit > 0
+    __device__ __forceinline__ bool at_most(float limit) const {
+        return pos <= __float_as_int(limit) && neg <= (0x80000000u | (unsigned)__float_as_int(limit));
+    }
+    __device__ __forceinline__ bool below(float limit) const {
+        return pos < __float_as_int(limit) && neg < (0x80000000u | (unsigned)__float_as_int(limit));
+    }
+};
+
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + expf(-x)); }
 
 __device__ __forceinline__ int reflect101(int i, int n) {

@@ -221,13 +221,13 @@ __global__ __launch_bounds__(256, (conv_wgs_per_cu<KS, STRIDE, KC, TN>())) void 
                                                  16, 0, 0);
         }
     };
-    float amax = 0.0f;                                         // largest |activation| staged for a half-precision operand path
+    YondRange amax;                                             // largest |activation| staged for a half-precision operand path
     auto write_item = [&](float* buf, int k) {
         f32x4 v = vin[k];
         if (PRE) { v[0] = silu_fast(v[0]); v[1] = silu_fast(v[1]); v[2] = silu_fast(v[2]); v[3] = silu_fast(v[3]); }
         const f32x4 z = {0.0f, 0.0f, 0.0f, 0.0f};
         v = ((vin_ok >> k) & 1u) ? v : z;                                                         // conv zero padding
-        if (MODE != 0) amax = fmaxf(amax, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));   // range guard
+        if (MODE != 0) amax.add(v);   // range guard
         if (SPL) v = split_pack4(v);
         if ((YOND_ABL & 2) == 0) *(f32x4*)(buf + in_lds[k]) = v;
     };
@@ -509,7 +509,7 @@ __global__ __launch_bounds__(256, (conv_wgs_per_cu<KS, STRIDE, KC, TN>())) void 
             if ((YOND_ABL & 4) == 0) epilogue_from(prev, eacc, ppar);
         }
     }
-    if (MODE != 0 && d.status && !(amax <= 65504.0f)) atomicOr(d.status, YOND_STATUS_HALF_OVERFLOW);
+    if (MODE != 0 && d.status && !amax.at_most(65504.0f)) atomicOr(d.status, YOND_STATUS_HALF_OVERFLOW);
 }
 
 template <int KS, int STRIDE, int TH, int TN, int KC, bool PRE, int MODE>

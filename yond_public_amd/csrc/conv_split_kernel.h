@@ -12,6 +12,10 @@
 // (tests/test_hip_conv.py::test_conv3x3_split_accuracy_beside_fp32_kernels) the error is that of the fp32 direct kernel.
 // Limits: |a| < 65504 (fp16 max); an operand below fp16's normal range (|a| < 6.1e-5) keeps an absolute error of 2^-36
 // instead of a relative one.  Activations and weights of the denoisers are O(1).
+// Range guard: a value beyond the limit, +-inf or NaN sets YOND_STATUS_HALF_OVERFLOW where it BECOMES halves -- when it is staged from an
+// fp32 tensor, or by the producer that stores split planes / h-only planes / the second output.  A consumer of finished planes (LDS-DMA)
+// cannot see the value: it raises nothing and answers with NaN / inf; the host repeats the forward on the producer's flag.
+// (tests/split_model.py: the arithmetic's model and per-output bound; tests/test_hip_split_stress.py, test_hip_range_guard.py hold every form to them.)
 // With PARTS = 1 (descriptor algo 4) only the h halves are staged and multiplied: the plain fp16 MFMA path of
 // BASELINE cfg 5 (fp32 tensors in HBM, fp32 accumulate), without the per-fragment conversions of conv.hip's mode 1.
 //
@@ -370,7 +374,7 @@ __global__ __launch_bounds__(64 * NWAVE, (NWAVE == 4 && STRIDE == 1) ? 2 : 1) vo
     static_assert(NSET == 3 || C::WAHEAD == 1, "the two-set pipeline goes with two weight buffers");
     f32x4 vin[NSET][NINA];
     unsigned vin_ok[NSET] = {};
-    float amax = 0.0f;                                         // largest |activation| this thread has staged (range guard)
+    YondRange amax;                                             // largest |activation| this thread has staged (range guard)
     // one 16-byte load of a set (item k); the source of the chunk is selected once per step (LoadSrc)
     // source of a step's 16-channel chunks (K1: three of them, each from the low-resolution input or from the skip tensor)
     // (address of an item = src + pixel offset * A + B: [N][H][W][C] float32: A = C, B = chunk channel + 4 slot; planes of 4
@@ -508,7 +512,7 @@ __global__ __launch_bounds__(64 * NWAVE, (NWAVE == 4 && STRIDE == 1) ? 2 : 1) vo
         vin[P][k][j] = ((vin_ok[P] >> k) & 1u) ? x : 0.0f;                              // conv zero padding
         if constexpr (j == 3) {
             const f32x4 v = vin[P][k];
-            amax = fmaxf(amax, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));   // two v_max3
+            amax.add(v);   // four integer max3
             const f16x4 h = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
             *(f16x4*)(ob + in_lds[k]) = h;
             if constexpr (PARTS == 2) {
@@ -989,7 +993,7 @@ __global__ __launch_bounds__(64 * NWAVE, (NWAVE == 4 && STRIDE == 1) ? 2 : 1) vo
                         if constexpr (HAS_RES) y += (m < LR0 ? qrr[m < LR0 ? m : 0][nn][g][e] : lrr[m >= LR0 ? m - LR0 : 0][nn][g][e]);
                         v[e] = y;
                     }
-                    amax = fmaxf(amax, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
+                    amax.add(v);
                     const f16x4 h = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
                     char* pp = pb + (size_t)(oy * d.Wo + ox) * 16;
                     if (ok) *(f16x4*)pp = h;
@@ -1063,7 +1067,7 @@ __global__ __launch_bounds__(64 * NWAVE, (NWAVE == 4 && STRIDE == 1) ? 2 : 1) vo
                         f32x4 a;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) a[e] = split_silu(v[e]);
-                        amax = fmaxf(amax, fmaxf(fmaxf(fabsf(a[0]), fabsf(a[1])), fmaxf(fabsf(a[2]), fabsf(a[3]))));
+                        amax.add(a);
                         const f16x4 h = {(_Float16)a[0], (_Float16)a[1], (_Float16)a[2], (_Float16)a[3]};
                         const int c8 = cbase - 4 * lh + 8 * g;                          // first channel of the lane's unit
                         const size_t PS2 = (size_t)yond_sp_plane_units(Hout, Wout);
@@ -1291,7 +1295,7 @@ __global__ __launch_bounds__(64 * NWAVE, (NWAVE == 4 && STRIDE == 1) ? 2 : 1) vo
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the look-ahead loads / DMA of the steps past the end
-    if (d.status && !(amax <= 65504.0f)) atomicOr(d.status, YOND_STATUS_HALF_OVERFLOW);   // an h half became +-inf
+    if (d.status && !amax.at_most(65504.0f)) atomicOr(d.status, YOND_STATUS_HALF_OVERFLOW);   // an h half became +-inf
     if (clk_on) {
         atomicAdd(d.clk, __builtin_amdgcn_s_memtime() - clk_c0);
         atomicAdd(d.clk + 1, __builtin_amdgcn_s_memrealtime() - clk_r0);

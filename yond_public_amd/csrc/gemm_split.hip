@@ -133,7 +133,9 @@ __global__ __launch_bounds__(256) void gemm_split_kernel(const GsArgs a) {
             wbad |= (v[0] != v[0]) | (v[1] != v[1]) | (v[2] != v[2]) | (v[3] != v[3]);
             wmax = fmaxf(wmax, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
             const gs_f16x4 h = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
-            const gs_f16x4 P = {(_Float16)(v[0] * 2048.0f), (_Float16)(v[1] * 2048.0f), (_Float16)(v[2] * 2048.0f), (_Float16)(v[3] * 2048.0f)};
+            // P = 2^11 h EXACTLY (from h, not from v: below fp16's normal range fp16(2^11 v) keeps bits that h has lost and l holds too --
+            // the sum of the three products would count them twice, an error of |v - h| <= 2^-25 per operand instead of 2^-36)
+            const gs_f16x4 P = {(_Float16)((float)h[0] * 2048.0f), (_Float16)((float)h[1] * 2048.0f), (_Float16)((float)h[2] * 2048.0f), (_Float16)((float)h[3] * 2048.0f)};
             const gs_f16x4 l = {(_Float16)((v[0] - (float)h[0]) * 2048.0f), (_Float16)((v[1] - (float)h[1]) * 2048.0f),
                                 (_Float16)((v[2] - (float)h[2]) * 2048.0f), (_Float16)((v[3] - (float)h[3]) * 2048.0f)};
             *(gs_f16x4*)&s_w[buf][gi >> 3][0 * 64 + 8 * (gi & 7)] = P;

@@ -94,7 +94,7 @@ __global__ __launch_bounds__(512) void wgrad_split_kernel(const WgsGeom g) {
         const int left = (g.total - G0 + SK - 1) / SK;
         if (nsteps > left) nsteps = left;
     }
-    float amax = 0.0f;
+    YondRange amax;
     // with_bias: the bias gradient db[co] = sum over pixels of dY rides along -- every dY value passes through stage_dy exactly
     // once per output-channel group, so the workgroups of input-channel group 0 add up what they stage (a pass of its own over
     // dY cost 27 us per layer)
@@ -137,10 +137,12 @@ __global__ __launch_bounds__(512) void wgrad_split_kernel(const WgsGeom g) {
         return dyb + (unsigned)((((buf * PA + tile) * 3 + part) * SK + o) * 64 + c4 * 8);
     };
     auto stage_dy = [&](const f32x4& v, int buf, int tile, int o, int c4, f32x4& sum, bool count) {
-        amax = fmaxf(amax, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
+        amax.add(v);
         if (count) { sum[0] += v[0]; sum[1] += v[1]; sum[2] += v[2]; sum[3] += v[3]; }
         const f16x4 h = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
-        const f16x4 P = {(_Float16)(v[0] * 2048.0f), (_Float16)(v[1] * 2048.0f), (_Float16)(v[2] * 2048.0f), (_Float16)(v[3] * 2048.0f)};
+        // P = 2^11 h EXACTLY (from h, not from v: below fp16's normal range fp16(2^11 v) keeps bits that h has lost and l holds too --
+        // the sum of the three products would count them twice, an error of |v - h| <= 2^-25 per operand instead of 2^-36)
+        const f16x4 P = {(_Float16)((float)h[0] * 2048.0f), (_Float16)((float)h[1] * 2048.0f), (_Float16)((float)h[2] * 2048.0f), (_Float16)((float)h[3] * 2048.0f)};
         const f16x4 l = {(_Float16)((v[0] - (float)h[0]) * 2048.0f), (_Float16)((v[1] - (float)h[1]) * 2048.0f),
                          (_Float16)((v[2] - (float)h[2]) * 2048.0f), (_Float16)((v[3] - (float)h[3]) * 2048.0f)};
         *(f16x4*)d_dst(buf, tile, 0, o, c4) = P;
@@ -316,7 +318,7 @@ __global__ __launch_bounds__(512) void wgrad_split_kernel(const WgsGeom g) {
         __syncthreads();
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // (the loads of the batches past the end)
-    if (g.status && !(amax < 31.9f)) atomicOr(g.status, 1);      // a P part (2^11 dy) left fp16's range
+    if (g.status && !amax.below(31.9f)) atomicOr(g.status, 1);      // a P part (2^11 dy) left fp16's range
 
     // ---- the workgroup's partial tiles -> ws[slice][tap][Co][Ci] (x 2^-11: the products' common factor) ----
     // Accumulator layout: lane l holds column (ci) l % 32, rows (co) (r & 3) + 8 (r >> 2) + 4 (l / 32).  Stored from there a
