@@ -46,7 +46,14 @@ int yond_abi_version(void);
  * Arithmetic: float32 x*scale, then float64 in NumPy's staging with three shortcuts that stay below 1e-12 relative --
  * sqrt as a float32 estimate + one float64 Newton step, the LUT as per-interval coefficients a + b x, (v - lo) times the
  * reciprocal span -- and ONE rounding to float32: the result differs from the staged float64 evaluation by at most one
- * float32 ulp, and only where that evaluation lies within 1e-12 of a rounding boundary. */
+ * float32 ulp, and only where that evaluation lies within 1e-12 of a rounding boundary.  One exception, from the LUT's interval
+ * lookup (one multiply on evenly spaced runs of knots, csrc/lut_table.h): a pixel within 1e-3 of a step of a knot may be evaluated
+ * on the neighbouring interval, which moves the float64 value by at most |slope_next - slope_prev| * |x - knot| / (hi - lo)
+ * (< 1e-9 on get_bias' tables).  tests/vst_model.py restates the evaluation and the bound; tests/test_hip_vst_edges.py asserts it
+ * per element for every K1 entry point.
+ * NaN / Inf pixels: the clamp is fminf(fmaxf(u, 0), 1), which returns the other operand for a NaN -- a NaN pixel gives 0 in every
+ * mode and through every K1 entry point (torch.clamp would hand the NaN on to the network), and img_max ignores it; -inf gives 0;
+ * +inf gives 1 without a bias LUT (with one it lies beyond the last knot, where the 1-D LUT has no value). */
 int yond_pack_vst_norm_f32(const float* bayer, int H, int W, float* out, int pad_l, int pad_r, int pad_t,
                            int pad_b, int mode, double scale, double gain, double sigma, double lo,
                            double hi, const double* lut_x, const float* lut_y, int lut_n, float* img_max,
@@ -71,7 +78,10 @@ int yond_bias_eval_f32(const float* x, size_t n, const double* lut_x, const void
  * Replaces YOND_SIDD.py:286 (output clamp), :289-299 and utils/isp_algos.py:17-33 (inverse_VST).
  *   net_out  [Hp][Wp][4];  bayer_out [2h][2w];  crop origin (pad_t, pad_l)
  *   mode 0: identity (Simple_Denoiser :244-248), 1: algebraic inverse, 2: closed-form exact inverse
- *   clip01: apply the caller's .clip(0,1) (YOND_SIDD.py:389,407). */
+ *   clip01: apply the caller's .clip(0,1) (YOND_SIDD.py:389,407).
+ * One rounding to float32 of the float64 evaluation; mode 2 maps z <= 0 to 0 as the reference's masked assignment does.
+ * NaN / Inf inputs: the input clamp fminf(fmaxf(y, 0), 1) takes a NaN (and -inf) as 0 and +inf as 1 -- the output is finite for any input
+ * (torch.clamp would keep the NaN). */
 int yond_denorm_ivst_unpack_f32(const float* net_out, int Hp, int Wp, int pad_t, int pad_l, int h, int w,
                                 float* bayer_out, int mode, double scale, double gain, double sigma,
                                 double lo, double hi, int clip01, void* stream);
@@ -384,7 +394,10 @@ int yond_bias_lut_f64(const double* lams, int n, double gain, double sigma, floa
 /* N1  per-block PSNR / SSIM partial sums (YOND_SIDD.py:649-652, 679-697).  dn, hr: Bayer [H][W]; blocks of
  * bh x bw (row-major block order); out: [nblocks][ntiles][2] float64 = {sum of squared error, sum of SSIM
  * over the 'valid' map} per 32x32 tile, ntiles = yond_block_metrics_tiles(bh, bw); the host adds the tiles:
- * psnr = 10 log10(1 / (sum_se / (bh*bw))), ssim = sum_ssim / ((bh-10)*(bw-10)). */
+ * psnr = 10 log10(1 / (sum_se / (bh*bw))), ssim = sum_ssim / ((bh-10)*(bw-10)).
+ * Blocks smaller than 11 x 11 (no 'valid' position) are YOND_EINVAL.  The tiles of a block are one grid dimension of the launch: a block
+ * of more than 65,535 tiles (beyond about 8,160 x 8,160) is refused -- yond_block_metrics_tiles returns YOND_EUNSUPPORTED, and
+ * yond_block_metrics_f32 returns the same before it launches anything. */
 int yond_block_metrics_tiles(int bh, int bw);
 int yond_block_metrics_f32(const float* dn, const float* hr, int H, int W, int bh, int bw, double* out,
                            void* stream);

@@ -50,6 +50,9 @@ def test_host_side_argument_checks_without_gpu():
     # null pointers are rejected before any launch
     assert lib.yond_pack_vst_norm_f32(None, 4, 4, None, 0, 0, 0, 0, 1, 1.0, 1.0, 0.0, 0.0, 1.0, None, None, 0, None, None) == -1
     assert lib.yond_conv2d_f32(None, None) == -1
+    # the block metrics' tiles are one grid dimension: more than 65,535 of them are refused (8192 + 32 squared: 257 * 257 tiles)
+    assert lib.yond_block_metrics_tiles(8192 + 32, 8192 + 32) == -2 and lib.yond_block_metrics_tiles(8160, 8160) == 255 * 255
+    assert lib.yond_block_metrics_tiles(10, 256) == -1 and lib.yond_block_metrics_tiles(256, 256) == 64
 
 
 def test_weight_packing_layout():

@@ -119,14 +119,19 @@ __global__ __launch_bounds__(256) void block_metrics_kernel(const float* __restr
     }
 }
 
+// tiles of one block: they are the launch's blockIdx.y, so a block of more than 65,535 tiles (beyond about 8,160 x 8,160) is refused
+#define METRICS_MAX_TILES 65535
 extern "C" int yond_block_metrics_tiles(int bh, int bw) {
     if (bh < 11 || bw < 11) return YOND_EINVAL;
-    return ((bh + MT - 1) / MT) * ((bw + MT - 1) / MT);
+    const long long nt = (long long)((bh + MT - 1) / MT) * ((bw + MT - 1) / MT);
+    if (nt > METRICS_MAX_TILES) return YOND_EUNSUPPORTED;
+    return (int)nt;
 }
 
 extern "C" int yond_block_metrics_f32(const float* dn, const float* hr, int H, int W, int bh, int bw, double* out,
                                       void* stream) {
     if (!dn || !hr || !out || bh < 11 || bw < 11 || H < bh || W < bw || H % bh || W % bw) return YOND_EINVAL;
+    if (const int nt = yond_block_metrics_tiles(bh, bw); nt < 0) return nt;                // (more tiles than blockIdx.y holds)
     const int nbx = W / bw, nby = H / bh;
     const int ntx = (bw + MT - 1) / MT, nty = (bh + MT - 1) / MT;
     const size_t smem = sizeof(double) * (5 * MH * MT) + sizeof(float) * (2 * MH * MH);

@@ -2142,10 +2142,14 @@ def _side_stream(dev, which='side'):
 def block_metrics(dn, hr, bh=256, bw=256):
     """Per-block PSNR (data_range 1) and SSIM (x255, 11x11 Gaussian, valid) -> two float64 arrays."""
     lib = L.load()
+    nt = lib.yond_block_metrics_tiles(bh, bw)                     # (refused before anything is copied or launched)
+    if nt == -2:
+        raise L.YondHipError(f"block_metrics: a {bh} x {bw} block has more than 65535 tiles of 32 x 32 (the launch's limit: about 8160 x 8160)")
+    if nt < 0:
+        raise L.YondHipError(f"block_metrics: blocks of {bh} x {bw} are smaller than the 11 x 11 SSIM window")
     dn, hr = _dev(dn), _dev(hr, dn.device if isinstance(dn, torch.Tensor) else None)
     H, W = dn.shape
     nblk = (H // bh) * (W // bw)
-    nt = lib.yond_block_metrics_tiles(bh, bw)
     out = torch.empty((nblk, nt, 2), dtype=torch.float64, device=dn.device)
     L.check(lib.yond_block_metrics_f32(L.ptr(dn), L.ptr(hr), H, W, bh, bw, L.ptr(out), L.stream()), "yond_block_metrics_f32")
     s = out.sum(dim=1).cpu().numpy()
