@@ -402,6 +402,41 @@ int yond_block_metrics_tiles(int bh, int bw);
 int yond_block_metrics_f32(const float* dn, const float* hr, int H, int W, int bh, int bw, double* out,
                            void* stream);
 
+/* N1 on sRGB codes (YOND_SIDD.py:657-677, 712-717 calculate_ssim on a three-channel image).  dn, hr: interleaved uint8 [H][W][3];
+ * out: [nblocks][ntiles][3][2] float64 = per channel {sum of squared code error, sum of SSIM over the 'valid' map} per 32x32 tile.
+ * The same kernel as yond_block_metrics_f32 on a uint8 loader: the codes ARE the [0,255] values (no x255), same window, C1, C2 and
+ * refusals.  The host adds the tiles: psnr_rgb = 10 log10(255^2 / (sum_se over the 3 channels / (3*bh*bw))), ssim_rgb = the mean
+ * of the three channels' sum_ssim / ((bh-10)*(bw-10)). */
+int yond_block_metrics_rgb8(const unsigned char* dn, const unsigned char* hr, int H, int W, int bh, int bw, double* out,
+                            void* stream);
+
+/* R1  raw Bayer frame -> sRGB (isp.hip; utils/sidd_utils.py:156-277 process_sidd_image, utils/isp_ops.py:171-197 FastISP).
+ *   frame      float32 (device): layout YOND_ISP_BAYER [H][W], or YOND_ISP_PACKED4 [H/2][W/2][4] in R, G1, G2, B order; H, W even
+ *   flip_lr/ud the frame is read mirrored (flip_bayer, sidd_utils.py:182-196: brings the pattern to RGGB); Bayer layout only
+ *   gains      float64 [4] (host), one per CFA site of the RGGB frame (R, G1, G2, B)
+ *   ccm        float64 [9] (host), row-major camera -> sRGB matrix
+ *   mode       YOND_ISP_SIDD: clip(0,1), float32 x float64 gain in float64, clip(0,1), x16383.0, clip, truncate; the demosaiced
+ *              integer / 16383 is a float32 division.  YOND_ISP_FAST: the gained value is rounded to float32 (FastISP stages the
+ *              frame in float32), clipped, x16383 in float32, truncated; the quotient is a float64 division.
+ *   demosaic   on the integers, RGGB, neighbours outside the frame mirrored without repeating the edge (-1 -> 1, H -> H-2).  R / B
+ *              site: own colour = q; G = (up+down+1)>>1 if |left-right| > |up-down| else (left+right+1)>>1; the opposite colour =
+ *              (four diagonals + 2)>>2.  G site: the horizontal neighbours' colour = (left+right+1)>>1, the other = (up+down+1)>>1.
+ *              This is the project's restatement of cv2's COLOR_BayerBG2RGB_EA: UNPINNED.
+ *   colour     x_r = (d0*M[r][0] + d1*M[r][1]) + d2*M[r][2] in float64, no contraction, then clip(0,1)
+ *   out_u8     (nullable, 4-byte aligned) uint8 [H][W][3], order YOND_ISP_RGB or YOND_ISP_BGR: code = #{k in 1..255 : thresholds[k-1]
+ *              <= x}, thresholds float64 [255] (device) = (k/255)^2.2 -- trunc(max(x,1e-8)^(1/2.2) * 255) away from the thresholds
+ *   out_f32    (nullable) float32 [H][W][3] RGB = x^(1/gamma), pow in float64 rounded once
+ * Refused (YOND_EINVAL, nothing launched): a null frame / gains / ccm, H or W odd or < 2, both outputs null, out_u8 without
+ * thresholds or misaligned, an unknown layout / mode / order, flips with the packed layout, gamma <= 0 with out_f32. */
+#define YOND_ISP_BAYER 0
+#define YOND_ISP_PACKED4 1
+#define YOND_ISP_SIDD 0
+#define YOND_ISP_FAST 1
+#define YOND_ISP_RGB 0
+#define YOND_ISP_BGR 1
+int yond_render_srgb(const float* frame, int H, int W, int flip_lr, int flip_ud, int layout, const double* gains, const double* ccm,
+                     int mode, const double* thresholds, unsigned char* out_u8, int order, float* out_f32, double gamma, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * The per-frame parameter chain on the device: no host round trip between the estimator and the network.
  * Replaces the host arithmetic of YOND_SIDD.py:341-356 (beta -> K, sigma), :438-447 (round-2 guards), :263-264, 284-285

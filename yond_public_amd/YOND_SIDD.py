@@ -7,7 +7,9 @@ Same runfile schema (`pipeline`, `dst*`, `arch`), same class / method names (`YO
 `VST_Denoiser`, `Simple_Denoiser`), same model lookup by name and checkpoint search order.  Differences that
 are the point of this build: every per-pixel pass runs on the MI355X HIP kernels; images are sharded one per
 GPU process (image k -> rank k mod world) instead of nn.DataParallel over batch 1; per-block PSNR/SSIM are
-computed on the device and reduced with ONE all-reduce at the end.
+computed on the device and reduced with ONE all-reduce at the end.  `--fig` turns the reference's save_plot on (`--nofig` is
+`store_true` with default True there too, so it can never be turned off: :731): frames rendered to sRGB by the HIP kernel
+(yond_public_amd/isp.py), PNGs under the sample directory, PSNR(sRGB) / SSIM(sRGB) beside the raw metrics (:635-677, 551-563).
 
 Datasets: the reference's SIDD layout (`<root_dir>/SIDD_Validation_Raw/Validation{Noisy,Gt}BlocksRaw.mat`, MATLAB v5, plus
 `SIDD_Benchmark_Data/*/*_010.MAT` metadata: yond_public_amd/data.py mirrors data_process/yond_datasets.py:767-868), or
@@ -138,6 +140,8 @@ class YOND_SIDD:
             self.pipe['bias_corr'] = None
         self.model_name, self.method_name = self.args['model_name'], self.args['method_name']
         self.fast_ckpt = self.args['fast_ckpt']
+        self.save_plot = bool(getattr(self.parser, 'fig', False))                    # YOND_SIDD.py:153
+        self.sample_dir = os.path.join(str(self.args.get('result_dir', './images')), f"{self.method_name}")        # :170
         os.makedirs('./logs', exist_ok=True)
         self.logfile = f'./logs/log_{self.method_name}.log' if self.rank == 0 else None
         # model: looked up by name, checkpoint search order best -> last -> plain (YOND_SIDD.py:177-184)
@@ -216,6 +220,59 @@ class YOND_SIDD:
             res['hr_raw'] = cat(d['hr']) if d.get('hr') is not None else None
         return ress
 
+    # -- sRGB rendering (--fig) -----------------------------------------------------------------
+    @staticmethod
+    def _fig_tag(name):
+        """name[:4] (YOND_SIDD.py:638: the SIDD scene number); the whole name where that is no number (the stand-ins)."""
+        return name[:4] if name[:4].isdigit() else name
+
+    def _render(self, data, raw):
+        """process_sidd_image of one Bayer frame with the item's metadata -> device uint8 [H][W][3] RGB.  Items without metadata (the
+        synthetic stand-ins, .npy blocks) render as RGGB with wb = 1 and the identity as the camera -> sRGB matrix."""
+        from . import isp
+        if data.get('meta') is not None and data.get('wb') is not None and data.get('ccm') is not None:
+            return isp.render_sidd(raw, data['cfa'], data['wb'], data['ccm'], order='rgb')
+        return isp.render_sidd(raw, isp.RGGB, [[1.0, 1.0, 1.0]], None, order='rgb', ccm=np.eye(3))
+
+    def _save_png(self, path, img):
+        """PNG encoding on a host thread: the device goes on with the next image."""
+        from concurrent.futures import ThreadPoolExecutor
+        from . import isp
+        if getattr(self, '_png_pool', None) is None:
+            self._png_pool, self._png_jobs = ThreadPoolExecutor(max_workers=2), []
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        self._png_jobs.append(self._png_pool.submit(isp.save_png, path, img.cpu().numpy()))
+
+    def _png_wait(self):
+        for job in getattr(self, '_png_jobs', None) or []:
+            job.result()
+        self._png_jobs = []
+
+    def figures(self, data, res):
+        """multiprocess_plot's save_plot part (YOND_SIDD.py:635-677) for one image: the concatenated 256 x 8192 noisy frame, the ground
+        truth and every round's output rendered whole (the demosaic crosses the block seams as in the reference), written as PNGs, and
+        the per-image sRGB metrics over the 32 blocks along the width.  Returns (psnrs_rgb, ssims_rgb), None where a round was skipped."""
+        from . import isp
+        tag = self._fig_tag(data['name'])
+        self._save_png(f'{self.sample_dir}/{tag}_noisy.png', self._render(data, res['lr_raw']))
+        img_hr = None
+        if res.get('hr_raw') is not None:
+            img_hr = self._render(data, res['hr_raw'])
+            self._save_png(f'{self.sample_dir}/{tag}_gt.png', img_hr)
+        psnrs, ssims = [], []
+        for it, dn in enumerate(res['raw_dns']):
+            if float(dn.max()) <= 0:                                                   # :644-647
+                psnrs.append(None)
+                ssims.append(None)
+                continue
+            img_dn = self._render(data, dn)
+            self._save_png(f'{self.sample_dir}/{tag}_{it}.png', img_dn)
+            if img_hr is not None:
+                ps, ss = isp.block_metrics_rgb(img_dn, img_hr, 256, img_dn.shape[1] // 32)          # :661-665
+                psnrs.append(float(np.mean(ps)))
+                ssims.append(float(np.mean(ss)))
+        return psnrs, ssims
+
     def _groups(self, it):
         """The prefetcher's items `group` at a time (consecutive items; the last group may be short)."""
         G = max(1, int(getattr(self.parser, 'group', 1)))
@@ -230,7 +287,8 @@ class YOND_SIDD:
 
     def eval(self, epoch=-1):
         n_it = self.pipe['max_iter'] + 1 if self.pipe.get('iter') == 'iter' else 1
-        sums = D.MetricSums(n_it)
+        fig = bool(getattr(self, 'save_plot', False))        # --fig: everything below is today's path without it
+        sums = D.MetricSums(n_it, rgb=True) if fig else D.MetricSums(n_it)
         p = dict(self.pipe)
         p.update({'wp': 1023, 'bl': 64, 'ratio': 1, 'gain': 1, 'sigma': 0})          # YOND_SIDD.py:504
         p['scale'] = (p['wp'] - p['bl']) / p['ratio']
@@ -250,6 +308,8 @@ class YOND_SIDD:
         est_type = str(self.pipe.get('est_type', 'simple'))
         streamed = (P.STREAM_GROUPS and getattr(self.parser, 'stream', True) and self.pipe.get('iter') == 'iter' and self.pipe.get('max_iter', 1) == 1
                     and 'simple' in est_type and 'cal_est' not in self.pipe and 'rot_cfa' not in p and self.biaslut is None)
+        if fig:
+            streamed = False                                 # the figures are rendered image by image behind IterDenoise
 
         def metrics_of(data, res):
             psnrs, ssims = [], []
@@ -263,11 +323,24 @@ class YOND_SIDD:
             return psnrs, ssims
 
         def account(data, res, psnrs, ssims):
-            if psnrs:
-                sums.update(psnrs, ssims)            # iterations that did not run count -1 in their own meter (:644-647)
-            self.metrics[data['name']] = {'psnr': psnrs, 'ssim': ssims, 'reg': res['regs']}
+            if not fig:
+                if psnrs:
+                    sums.update(psnrs, ssims)            # iterations that did not run count -1 in their own meter (:644-647)
+                self.metrics[data['name']] = {'psnr': psnrs, 'ssim': ssims, 'reg': res['regs']}
+            else:
+                if 'lr_raw' not in res:
+                    cat = lambda a: torch.cat(list(a), dim=-1) if isinstance(a, torch.Tensor) else np.concatenate(a, axis=-1)
+                    res['lr_raw'], res['hr_raw'] = cat(data['lr']), cat(data['hr']) if data.get('hr') is not None else None
+                psnrs_rgb, ssims_rgb = self.figures(data, res)
+                done = [(a, b) for a, b in zip(psnrs_rgb, ssims_rgb) if a is not None]
+                if psnrs and done:
+                    sums.update(psnrs, ssims, psnrs_rgb, ssims_rgb)
+                self.metrics[data['name']] = {'psnr': psnrs, 'ssim': ssims, 'reg': res['regs'],
+                                              'psnr_rgb': [a for a, _ in done], 'ssim_rgb': [b for _, b in done]}
             log(f"[rank {self.rank}] {data['name']}: PSNR={psnrs[-1] if psnrs else float('nan'):.2f}, "
                 f"SSIM={ssims[-1] if ssims else float('nan'):.4f}", self.logfile)
+            if fig and done:
+                log(f"PSNR(sRGB)={done[-1][0]:.2f}, SSIM(sRGB)={done[-1][1]:.4f}", self.logfile)           # :677
 
         if streamed:
             # consecutive groups overlapped on two HIP streams (pipeline.denoise_stream_groups): group k+1's full-frame estimates under group k's first
@@ -306,6 +379,7 @@ class YOND_SIDD:
             t_path += time.perf_counter() - t1              # estimate + denoise (+ metrics) of this group's images
             marks.extend([(time.perf_counter(), t_path)] * len(batch))
         torch.cuda.synchronize()
+        self._png_wait()
         dt = time.perf_counter() - t0
         red = sums.reduce(self.device)                 # the ONE collective of the eval path (RCCL over xGMI)
         dt = D.max_over_ranks(dt, self.device)
@@ -313,7 +387,11 @@ class YOND_SIDD:
             log(f'{self.method_name}:', self.logfile)
             for it in range(n_it):
                 log(f"Iter{it}: PSNR={red[f'psnr_iter{it}']:.2f}, SSIM={red[f'ssim_iter{it}']:.4f}", self.logfile)
+                if fig:                                                       # :555-557
+                    log(f"PSNR(sRGB)={red[f'psnr_rgb_iter{it}']:.2f}, SSIM(sRGB)={red[f'ssim_rgb_iter{it}']:.4f}", self.logfile, notime=True)
             log(f"Iter_last: PSNR={red['psnr_last']:.2f}, SSIM={red['ssim_last']:.4f}", self.logfile)
+            if fig:                                                           # :561-563
+                log(f"PSNR(sRGB)={red['psnr_rgb_last']:.2f}, SSIM(sRGB)={red['ssim_rgb_last']:.4f}", self.logfile, notime=True)
             log(f"{red['count']} images on {self.world} GPU(s) in {dt:.2f} s "
                 f"(rank 0: {dt / max(len(mine), 1) * 1e3:.1f} ms wall per image, {t_path / max(len(mine), 1) * 1e3:.1f} ms of it in IterDenoise + metrics; "
                 f"the rest is waiting for the {self.parser.loaders} loader threads)", self.logfile)
@@ -333,8 +411,9 @@ class YOND_SIDD:
         """YOND_SIDD.py:572-630 (`-m test`): the SIDD BENCHMARK blocks (no ground truth) through IterDenoise; keeps what the
         reference keeps -- per-image estimates as `reg_test` in self.metrics and the two submission arrays
         bench_init / bench_results [N][32][256][256] (first / last round) -- and writes them to npy/<method>/ (the reference's
-        .mat export is commented out upstream, :615-621; sRGB previews need cv2 and are out of scope).  Images are sharded over
-        the ranks; every rank writes the blocks of its own images."""
+        .mat export is commented out upstream, :615-621).  With --fig the noisy frame and every round's output are rendered to
+        sRGB and written as <sample_dir>/benchmark/<name[:4]>_noisy.png and _<it>.png (:600-608).  Images are sharded over the ranks;
+        every rank writes the blocks of its own images."""
         n = len(self.dst_eval)
         bench_init = np.zeros((n, 32, 256, 256), np.float32)
         bench_results = np.zeros((n, 32, 256, 256), np.float32)
@@ -356,8 +435,15 @@ class YOND_SIDD:
                 first, last = res['raw_dns'][0].cpu().numpy(), res['raw_dns'][-1].cpu().numpy()
                 bench_init[k] = np.array(np.split(first, 32, axis=-1))                                # :612-613
                 bench_results[k] = np.array(np.split(last, 32, axis=-1))
+                if getattr(self, 'save_plot', False):                                                 # :600-608
+                    tag = self._fig_tag(data['name'])
+                    self._save_png(f'{self.sample_dir}/benchmark/{tag}_noisy.png', self._render(data, res['lr_raw']))
+                    for it, dn in enumerate(res['raw_dns']):
+                        if float(dn.max()) > 0:
+                            self._save_png(f'{self.sample_dir}/benchmark/{tag}_{it}.png', self._render(data, dn))
                 log(f"[rank {self.rank}] {data['name']}: {len(res['raw_dns'])} round(s), regs {[tuple(float(v) for v in r) for r in res['regs']]}", self.logfile)
         torch.cuda.synchronize()
+        self._png_wait()
         dt = D.max_over_ranks(time.perf_counter() - t0, self.device)
         os.makedirs(f'npy/{self.method_name}', exist_ok=True)
         tag = '' if self.world == 1 else f'_rank{self.rank}'
@@ -378,7 +464,9 @@ class YONDParser:
         a.add_argument('--runfile', '-f', default="runfiles/YOND/SIDD_simple+full_pre_grumix.yml", type=Path, help="path to config")
         a.add_argument('--mode', '-m', default='eval', type=str, help="eval or test")
         a.add_argument('--debug', action='store_true', default=False)
-        a.add_argument('--nofig', action='store_true', default=True, help="don't save plots (no sRGB rendering in this build)")
+        a.add_argument('--nofig', action='store_true', default=True, help="kept for CLI compatibility (store_true with default True, as in the reference: it cannot be turned off); --fig turns the figures on")
+        a.add_argument('--fig', action='store_true', default=False, help="render the noisy frame, the ground truth and every round's output to sRGB on the GPU: "
+                       "PNGs under <result_dir>/<method_name>/ and PSNR(sRGB) / SSIM(sRGB) beside the raw metrics")
         a.add_argument('--nohost', action='store_true', default=False)
         a.add_argument('--gpu', default="0", help="kept for CLI compatibility; ranks pick their device from LOCAL_RANK")
         a.add_argument('--synthetic', type=int, default=40, help="number of synthetic stand-in images when no dataset is found "
@@ -394,6 +482,7 @@ class YONDParser:
 
 def main(argv=None):
     trainer = YOND_SIDD(argv)
+    main.trainer = trainer                                   # the last run's driver object (its .metrics, .sample_dir)
     try:
         out = None
         if 'eval' in trainer.mode:                           # YOND_SIDD.py:736-744

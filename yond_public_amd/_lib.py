@@ -90,6 +90,8 @@ PROTOTYPES = {
     "yond_bias_lut_f64": [vp, i32, f64, f64, vp, vp],
     "yond_block_metrics_tiles": [i32, i32],
     "yond_block_metrics_f32": [vp, vp, i32, i32, i32, i32, vp, vp],
+    "yond_block_metrics_rgb8": [vp, vp, i32, i32, i32, i32, vp, vp],
+    "yond_render_srgb": [vp, i32, i32, i32, i32, i32, C.POINTER(f64), C.POINTER(f64), i32, vp, vp, i32, vp, f64, vp],
     "yond_clock_probe": [f64, vp, vp],
     "yond_img2raw_f32": [vp, sz, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp],
     "yond_est_conv_in_f32": [vp, i32, i32, i32, i32, vp, vp, vp, vp],

@@ -11,8 +11,28 @@
 
 struct MetricsGauss { double g[11]; };       // the normalised 11-tap window, computed once on the host (every workgroup used to evaluate 121 float64 exponentials)
 
-__global__ __launch_bounds__(256) void block_metrics_kernel(const float* __restrict__ dn, const float* __restrict__ hr,
-                                                            int W, int bh, int bw, int nbx, int ntx,
+// Loaders: element idx of the two images -> the [0,255] values the SSIM sees (as floats) and the error the PSNR squares.
+struct MetricsLoadF32 {                      // Bayer float32 in [0,1]
+    const float* __restrict__ dn; const float* __restrict__ hr;
+    __device__ __forceinline__ void operator()(size_t idx, float& a, float& b, double& d) const {
+        const float fa = dn[idx], fb = hr[idx];
+        a = __fmul_rn(fa, 255.0f);                 // dn*255 is a float32 product (YOND_SIDD.py:652), then float64
+        b = __fmul_rn(fb, 255.0f);
+        d = (double)fa - (double)fb;
+    }
+};
+struct MetricsLoadRgb8 {                     // interleaved uint8 [H][W][3], channel = blockIdx.z: the codes are the values
+    const uint8_t* __restrict__ dn; const uint8_t* __restrict__ hr;
+    __device__ __forceinline__ void operator()(size_t idx, float& a, float& b, double& d) const {
+        const int ca = dn[idx * 3 + blockIdx.z], cb = hr[idx * 3 + blockIdx.z];
+        a = (float)ca;
+        b = (float)cb;
+        d = (double)(ca - cb);
+    }
+};
+
+template <class Load>
+__global__ __launch_bounds__(256) void block_metrics_kernel(const Load load, int W, int bh, int bw, int nbx, int ntx,
                                                             double* __restrict__ out, const MetricsGauss gw) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     double* s_q = sm;                      // [5][MH][MT]
@@ -33,10 +53,9 @@ __global__ __launch_bounds__(256) void block_metrics_kernel(const float* __restr
         float a = 0.0f, b = 0.0f;
         if (y < bh && x < bw) {
             const size_t idx = (size_t)(by * bh + y) * W + (size_t)bx * bw + x;
-            const float fa = dn[idx], fb = hr[idx];
-            a = __fmul_rn(fa, 255.0f);                 // dn*255 is a float32 product (YOND_SIDD.py:652), then float64
-            b = __fmul_rn(fb, 255.0f);
-            if (r < MT && c < MT) { const double d = (double)fa - (double)fb; se += d * d; }
+            double d;
+            load(idx, a, b, d);
+            if (r < MT && c < MT) se += d * d;
         }
         s_a[it] = a;
         s_b[it] = b;
@@ -113,7 +132,7 @@ __global__ __launch_bounds__(256) void block_metrics_kernel(const float* __restr
     if ((tid & 63) == 0) { s_red[tid >> 6] = se; s_red[4 + (tid >> 6)] = ss; }
     __syncthreads();
     if (tid == 0) {
-        double* o = out + ((size_t)blk * gridDim.y + tile) * 2;
+        double* o = out + (((size_t)blk * gridDim.y + tile) * gridDim.z + blockIdx.z) * 2;   // [block][tile][channel][2]
         o[0] = s_red[0] + s_red[1] + s_red[2] + s_red[3];
         o[1] = s_red[4] + s_red[5] + s_red[6] + s_red[7];
     }
@@ -128,9 +147,9 @@ extern "C" int yond_block_metrics_tiles(int bh, int bw) {
     return (int)nt;
 }
 
-extern "C" int yond_block_metrics_f32(const float* dn, const float* hr, int H, int W, int bh, int bw, double* out,
-                                      void* stream) {
-    if (!dn || !hr || !out || bh < 11 || bw < 11 || H < bh || W < bw || H % bh || W % bw) return YOND_EINVAL;
+template <class Load>
+static int block_metrics_launch(const Load load, int channels, int H, int W, int bh, int bw, double* out, void* stream) {
+    if (!load.dn || !load.hr || !out || bh < 11 || bw < 11 || H < bh || W < bw || H % bh || W % bw) return YOND_EINVAL;
     if (const int nt = yond_block_metrics_tiles(bh, bw); nt < 0) return nt;                // (more tiles than blockIdx.y holds)
     const int nbx = W / bw, nby = H / bh;
     const int ntx = (bw + MT - 1) / MT, nty = (bh + MT - 1) / MT;
@@ -142,16 +161,26 @@ extern "C" int yond_block_metrics_f32(const float* dn, const float* hr, int H, i
         for (int i = 0; i < 11; ++i) gs += exp(-((i - 5.0) * (i - 5.0)) / (2.0 * 1.5 * 1.5));
         for (int i = 0; i < 11; ++i) gw.g[i] = exp(-((i - 5.0) * (i - 5.0)) / (2.0 * 1.5 * 1.5)) / gs;
     }
-    static bool attr = false;
+    static bool attr = false;                                                              // (one per instantiation)
     if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)block_metrics_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        hipError_t e = hipFuncSetAttribute((const void*)block_metrics_kernel<Load>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         if (e != hipSuccess) return (int)e;
         attr = true;
     }
-    hipLaunchKernelGGL(block_metrics_kernel, dim3(nbx * nby, ntx * nty), dim3(256), smem, (hipStream_t)stream, dn, hr, W, bh, bw,
+    hipLaunchKernelGGL(block_metrics_kernel<Load>, dim3(nbx * nby, ntx * nty, channels), dim3(256), smem, (hipStream_t)stream, load, W, bh, bw,
                        nbx, ntx, out, gw);
     YOND_LAUNCH_CHECK();
     return YOND_OK;
+}
+
+extern "C" int yond_block_metrics_f32(const float* dn, const float* hr, int H, int W, int bh, int bw, double* out,
+                                      void* stream) {
+    return block_metrics_launch(MetricsLoadF32{dn, hr}, 1, H, W, bh, bw, out, stream);
+}
+
+extern "C" int yond_block_metrics_rgb8(const unsigned char* dn, const unsigned char* hr, int H, int W, int bh, int bw, double* out,
+                                       void* stream) {
+    return block_metrics_launch(MetricsLoadRgb8{dn, hr}, 3, H, W, bh, bw, out, stream);
 }
 
 

@@ -76,17 +76,23 @@ def shard_dataset(ds, rank, world):
 
 class MetricSums:
     """Per-rank sums of the per-image metrics, reduced once at the end.
-    Layout mirrors the reference's meters: [psnr_it0, ssim_it0, ..., psnr_last, ssim_last, count]."""
+    Layout mirrors the reference's meters: [psnr_it0, ssim_it0, ..., psnr_last, ssim_last, count].
+    rgb=True (the driver's --fig): the sRGB meters (eval_psnrs_rgb / eval_ssims_rgb, YOND_SIDD.py:203-206, 664-676) ride in the same
+    vector between the raw meters and the count -- [psnr_rgb_it, ssim_rgb_it, n_rgb_it] per iteration (a skipped iteration does NOT
+    update its sRGB meter, :644-647 `continue` in front of :666, so each keeps its own count), then [psnr_rgb_last, ssim_rgb_last] --
+    and the reduction is still ONE all-reduce.  With the default the vector is exactly the raw one."""
 
-    def __init__(self, n_iters):
-        self.n_iters = n_iters
-        self.vec = torch.zeros(2 * (n_iters + 1) + 1, dtype=torch.float64)
+    def __init__(self, n_iters, rgb=False):
+        self.n_iters, self.rgb = n_iters, bool(rgb)
+        self.vec = torch.zeros(2 * (n_iters + 1) + (3 * n_iters + 2 if rgb else 0) + 1, dtype=torch.float64)
 
-    def update(self, psnrs, ssims):
+    def update(self, psnrs, ssims, psnrs_rgb=None, ssims_rgb=None):
         """psnrs / ssims: the values of the iterations that RAN for one image (round 2 may have been ended by the
         reference's guard, YOND_SIDD.py:445-447).  Mirrors multiprocess_plot (:643-672): an iteration without output
         feeds -1 into ITS meter (:644-647, `continue`); the 'last' meter gets the last value that was computed
-        (:671-672 reuse the loop variables, which a skipped iteration leaves untouched)."""
+        (:671-672 reuse the loop variables, which a skipped iteration leaves untouched).
+        psnrs_rgb / ssims_rgb (rgb=True): one entry per iteration, None where it was skipped; the sRGB 'last' meter gets the last
+        value that was computed (:675-676)."""
         if not len(psnrs):
             raise ValueError("MetricSums.update needs the metrics of at least the first iteration")
         for it in range(self.n_iters):
@@ -94,6 +100,18 @@ class MetricSums:
             self.vec[2 * it + 1] += ssims[it] if it < len(ssims) else -1.0
         self.vec[2 * self.n_iters] += psnrs[-1]
         self.vec[2 * self.n_iters + 1] += ssims[-1]
+        if self.rgb:
+            done = [(p, s) for p, s in zip(psnrs_rgb or [], ssims_rgb or []) if p is not None and s is not None]
+            if not done:
+                raise ValueError("MetricSums(rgb=True).update needs the sRGB metrics of at least one iteration")
+            base = 2 * (self.n_iters + 1)
+            for it in range(min(self.n_iters, len(psnrs_rgb))):
+                if psnrs_rgb[it] is not None and ssims_rgb[it] is not None:
+                    self.vec[base + 3 * it] += psnrs_rgb[it]
+                    self.vec[base + 3 * it + 1] += ssims_rgb[it]
+                    self.vec[base + 3 * it + 2] += 1
+            self.vec[base + 3 * self.n_iters] += done[-1][0]
+            self.vec[base + 3 * self.n_iters + 1] += done[-1][1]
         self.vec[-1] += 1
 
     def reduce(self, device=None):
@@ -112,6 +130,14 @@ class MetricSums:
             out[f"ssim_iter{it}"] = float(v[2 * it + 1]) / max(cnt, 1)
         out["psnr_last"] = float(v[2 * self.n_iters]) / max(cnt, 1)
         out["ssim_last"] = float(v[2 * self.n_iters + 1]) / max(cnt, 1)
+        if self.rgb:
+            base = 2 * (self.n_iters + 1)
+            for it in range(self.n_iters):
+                n = max(float(v[base + 3 * it + 2]), 1)
+                out[f"psnr_rgb_iter{it}"] = float(v[base + 3 * it]) / n
+                out[f"ssim_rgb_iter{it}"] = float(v[base + 3 * it + 1]) / n
+            out["psnr_rgb_last"] = float(v[base + 3 * self.n_iters]) / max(cnt, 1)
+            out["ssim_rgb_last"] = float(v[base + 3 * self.n_iters + 1]) / max(cnt, 1)
         return out
 
 

@@ -22,7 +22,7 @@ reference's layout) holds one of two kinds of patch.
     (yond_datasets.py:308-320: sigma log-uniform in [sigma_min, sigma_max] / 255 when training, the fixed `dst_eval.sigma` with a
     per-index seed otherwise; Bayer-pattern augmentation by rotating the mosaic, :296-303).
 A directory mixing the two is refused before the first step.  Without data the trainer draws seeded synthetic patches so that
-the loop can be exercised and timed.  Plots, FastISP previews and the consistency branch (`command: consistency`) are not built.
+the loop can be exercised and timed.  Plots, FastISP previews (the function itself: utils/isp_ops.FastISP) and the consistency branch (`command: consistency`) are not wired in.
 """
 import argparse
 import math

@@ -1,5 +1,5 @@
 """Function seam of utils/isp_ops.py:57-71 -- Bayer <-> packed RGGB, bit-exact index permutations run
-as HIP copy kernels.  NumPy in -> NumPy out (as the reference), device tensor in -> device tensor out."""
+as HIP copy kernels.  NumPy in -> NumPy out (as the reference), device tensor in -> device tensor out -- and :171-197, FastISP."""
 import numpy as np
 import torch
 
@@ -34,3 +34,12 @@ def rggb2bayers(rggbs):
     H, W, _ = rggbs.shape[-3:]
     flat = rggbs.reshape(-1, H, W, 4)
     return torch.stack([_P.rggb2bayer(r) for r in flat])
+
+
+def FastISP(img4c, wb=None, ccm=None, gamma=2.2):
+    """utils/isp_ops.py:171-197: packed [h][w][4] (R, G1, G2, B; a tensor's [0] is taken, :173-174) -> [H][W][3] RGB float NumPy in
+    [0, 1], rendered by the HIP kernel (isp.fast_isp: float32, the reference returns float64)."""
+    from .. import isp as _isp
+    if torch.is_tensor(img4c):
+        img4c = img4c[0].detach()
+    return _isp.fast_isp(img4c, wb, ccm, gamma).cpu().numpy()

@@ -1,4 +1,5 @@
-"""Function seam of utils/sidd_utils.py for the path: rot_bayer (:198-213) and the SIDD metadata reader (:3-73)."""
+"""Function seam of utils/sidd_utils.py for the path: rot_bayer (:198-213), the SIDD metadata reader (:3-73) and the sRGB
+renderer process_sidd_image (:156-180)."""
 import numpy as np
 import torch
 
@@ -26,6 +27,16 @@ def rot_bayer(image, bayer_pattern, rev=False, axis=(-2, -1)):
     if tuple(a % image.dim() for a in axis) != (image.dim() - 2, image.dim() - 1):
         raise L.YondHipError("device rot_bayer rotates the last two axes")
     return _P.rot90(image, k)
+
+
+def process_sidd_image(image, bayer_pattern, wb, cst, *, save_file_rgb=None):
+    """utils/sidd_utils.py:156-180: Bayer frame [H][W] -> uint8 NumPy [H][W][3] in BGR order, rendered by the HIP kernel
+    (isp.render_sidd).  save_file_rgb: also written as a PNG (through PIL; the file holds RGB, as cv2.imwrite of a BGR array does)."""
+    from .. import isp as _isp
+    image_srgb = _isp.render_sidd(image, bayer_pattern, wb, cst, order='bgr').cpu().numpy()
+    if save_file_rgb:
+        _isp.save_png(save_file_rgb, image_srgb[:, :, ::-1])
+    return image_srgb
 
 
 def read_metadata(metadata):
