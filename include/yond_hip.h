@@ -660,6 +660,25 @@ int yond_est_head_f32(const float* feat, int N, int H, int W, int Cin, const flo
                       float* out, double* partial, void* stream);
 size_t yond_est_head_ws_bytes(int N, int out_nc);
 
+/* ------------------------------------------------------------------------------------------------
+ * R2 / R3  raw DN <-> the [0, 1] scale, the two ends of a full-frame run (rawio.hip; memory bound: 2 + 4, 4 + 4 and 4 + 2 B per pixel).
+ * Replaces the host normalisation of the full-frame datasets (data_process/yond_datasets.py:959-961, 1055-1056:
+ * (raw.astype(float32) - bl) * ratio / (wp - bl)) and writes a result back as integer DN.  Flat over n = H * W elements (a stack
+ * of frames is one call); pointers need only element alignment, n need not divide by anything.
+ *   yond_raw_ingest_u16 / _f32   out[i] = ((float)raw[i] - bl) * ratio / scale, then, with clip01 != 0, x < 0 ? 0 : (x > 1 ? 1 : x).
+ *       Three float32 operations, each rounded: subtract, multiply, IEEE divide (no reciprocal, no folded constant) -- bit-equal to
+ *       NumPy's evaluation with bl = float32(bl), ratio = float32(ratio), scale = float32(wp - bl) (the difference formed in
+ *       double), which is how NumPy takes the Python scalars.  A NaN stays a NaN through the clip, as through np.clip.
+ *   yond_raw_emit_u16            y = x[i] * scale; undo_gain != 0: y = y / ratio; y = y + bl; out[i] = (uint16) rint(min(max(y, 0),
+ *       65535)).  Every operation rounded on its own (no FMA), ties to even, NaN -> 0.  n_saturated (optional, device): ONE counter
+ *       to which the launch ADDS the number of elements whose y was NaN, < 0 or > 65535 (the caller zeroes it when it wants a
+ *       per-launch count).  emit(ingest(v), undo_gain) == v for every uint16 v <= wp (tests/test_rawio_host.py).
+ * Refused (YOND_EINVAL, nothing launched): a null raw / x / out, n == 0, a pointer that is not aligned to its element. */
+int yond_raw_ingest_u16(const uint16_t* raw, size_t n, float bl, float ratio, float scale, int clip01, float* out, void* stream);
+int yond_raw_ingest_f32(const float* raw, size_t n, float bl, float ratio, float scale, int clip01, float* out, void* stream);
+int yond_raw_emit_u16(const float* x, size_t n, float bl, float scale, float ratio, int undo_gain, uint16_t* out,
+                      unsigned long long* n_saturated, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

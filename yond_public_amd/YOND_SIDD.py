@@ -122,6 +122,8 @@ def load_estimators(args, device, logfile=None, beta=(4.0 / 959, 6.0 / 959)):
 
 
 class YOND_SIDD:
+    on_result = None               # callable(name, res): called with every image's result right before it is accounted
+
     def __init__(self, args=None):
         self.parser = YONDParser().parse(args)
         self.initialization()
@@ -286,6 +288,22 @@ class YOND_SIDD:
             yield batch
 
     def eval(self, epoch=-1):
+        """`--save f32` keeps every image's rounds as the reference does (YOND_SIDD.py:512-536): npy/<method_name>/<k:03d>.npy, float32
+        [max_iter + 1][256][8192] (rounds that did not run stay zero), written behind the GPU loop by a rawio.FrameWriter."""
+        save = getattr(self.parser, 'save', 'none')
+        if save == 'dn16':
+            raise SystemExit("YOND_SIDD eval keeps the reference's float32 cache: use --save f32")
+        writer = None
+        if save == 'f32':
+            from .rawio import FrameWriter
+            writer = FrameWriter(f'npy/{self.method_name}', 'f32')
+        try:
+            return self._eval(writer)
+        finally:
+            if writer is not None:
+                writer.close()
+
+    def _eval(self, writer):
         n_it = self.pipe['max_iter'] + 1 if self.pipe.get('iter') == 'iter' else 1
         fig = bool(getattr(self, 'save_plot', False))        # --fig: everything below is today's path without it
         sums = D.MetricSums(n_it, rgb=True) if fig else D.MetricSums(n_it)
@@ -321,6 +339,17 @@ class YOND_SIDD:
                     psnrs.append(float(np.mean(ps)))
                     ssims.append(float(np.mean(ss)))
             return psnrs, ssims
+
+        def keep(k, data, res):
+            if callable(self.on_result):
+                self.on_result(data['name'], res)
+            if writer is not None:
+                dns = res['raw_dns']
+                outputs = torch.zeros((n_it,) + tuple(dns[0].shape), dtype=torch.float32, device=dns[0].device)      # :512
+                for it, dn in enumerate(dns):
+                    outputs[it].copy_(dn)
+                writer.put(f'{k:03d}', outputs, (p['bl'], p['wp'], p['ratio']),
+                           {'name': data['name'], 'rounds': [(float(q[0]), float(q[1])) for q in res.get('params', [])]})
 
         def account(data, res, psnrs, ssims):
             if not fig:
@@ -359,6 +388,7 @@ class YOND_SIDD:
                                                              log=(lambda s: log(s, self.logfile)) if self.parser.verbose else None, finish=finish)):
                 batch = batches.pop(gi)
                 for (k, data), res, (psnrs, ssims) in zip(batch, ress, done.pop(gi)):
+                    keep(k, data, res)
                     account(data, res, psnrs, ssims)
                 t_path = time.perf_counter() - t0          # (groups overlap: the path IS the wall clock here)
                 marks.extend([(time.perf_counter(), t_path)] * len(batch))
@@ -374,6 +404,7 @@ class YOND_SIDD:
                 ress = self.IterDenoiseGroup(datas, plist)
             for (k, data), res in zip(batch, ress):
                 psnrs, ssims = metrics_of(data, res)
+                keep(k, data, res)
                 account(data, res, psnrs, ssims)
             torch.cuda.synchronize()
             t_path += time.perf_counter() - t1              # estimate + denoise (+ metrics) of this group's images
@@ -477,6 +508,11 @@ class YONDParser:
         a.add_argument('--no-stream', dest='stream', action='store_false', default=True, help="one group at a time instead of consecutive groups overlapped on two HIP streams")
         a.add_argument('--group', type=int, default=4, help="images denoised together: round 1 of a group is ONE batch-(32 x group) forward, round 2 another "
                        "(per image the results are those of --group 1)")
+        a.add_argument('--save', choices=('none', 'dn16', 'f32'), default='none', help="keep the denoised frames: the full-frame drivers write every item's last round to "
+                       "<result_dir>/<method_name>/<name>.npy (+ .json) as uint16 DN (dn16: digital gain kept) or float32 in [0, 1] (f32); YOND_SIDD eval with f32 "
+                       "writes the reference's cache npy/<method_name>/<k:03d>.npy, float32 [max_iter + 1][256][8192]")
+        a.add_argument('--host-ingest', dest='host_ingest', action='store_true', default=False, help="full-frame drivers: normalise the raw frames on the host in "
+                       "NumPy and upload float32 (the earlier path) instead of uploading the raw DN and normalising on the device")
         return a.parse_args(args)
 
 

@@ -6,6 +6,7 @@ reference does not ship.  They are modelled on YOND_SIDD.py with the full-frame 
     python YOND_ELD.py  -f runfiles/YOND/ELD_simple+full_pre_grumix.yml  -m eval
     python YOND_LRID.py -f runfiles/YOND/LRID_simple+full_pre_grumix.yml -m eval
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 YOND_ELD.py -f ... -m eval
+    python YOND_any.py  -f runfiles/YOND/ANY_simple+full_pre_grumix.yml  -m eval --save dn16     # + <result_dir>/<method_name>/<name>.{npy,json}
 
 Per (camera,) ratio of the runfile's list the dataset is switched with `change_eval_ratio` (data_process/yond_datasets.py:912,
 1033), every frame goes through `IterDenoise` as ONE whole-frame forward per round (YOND_SIDD.py:387-389, 456-458) with
@@ -13,6 +14,11 @@ p = {wp, bl, ratio, scale = (wp - bl) / ratio} (:503-505), and PSNR / SSIM of th
 Frames are sharded one per GPU process (frame k -> rank k mod world); the metric sums are reduced with ONE all-reduce per
 ratio.  Datasets are `.npy`-converted trees (yond_public_amd/data.py: rawpy is not in this image); without any data the
 driver runs on seeded synthetic low-light frames of the runfile's H x W so that the control flow can be exercised and timed.
+
+The two ends of a frame's trip are kernels (yond_public_amd/rawio.py): the datasets hand the raw DN over as loaded (uint16 or
+float32), the loader threads upload them in that dtype and normalise on the device (`--host-ingest`: the NumPy expression on the
+host, as before); `--save dn16 | f32` writes every item's last round through a FrameWriter, as uint16 DN at the level of the frame
+the metrics were computed on (the digital gain kept) or as float32 in the [0, 1] scale, each with a JSON sidecar.
 """
 import os
 import time
@@ -52,6 +58,8 @@ class SyntheticFrames:
 
 
 class YOND_Full:
+    on_result = None               # callable(name, res): called with every item's result right before it is accounted, on the consumer stream
+
     def __init__(self, args=None):
         self.parser = YONDParser().parse(args)
         with open(self.parser.runfile, 'r', encoding='utf-8') as f:
@@ -119,6 +127,19 @@ class YOND_Full:
                                               if not isinstance(self.dst_eval, SyntheticFrames) else self.dst_eval.change_eval_ratio(ratio=r))
 
     def eval(self, epoch=-1):
+        save = getattr(self.parser, 'save', 'none')
+        writer = None
+        if save != 'none':
+            from .rawio import FrameWriter
+            self.save_dir = os.path.join(str(self.args.get('result_dir', './images')), f'{self.method_name}')
+            writer = FrameWriter(self.save_dir, save)        # (under torchrun every rank writes its own frames)
+        try:
+            return self._eval(writer)
+        finally:
+            if writer is not None:
+                writer.close()
+
+    def _eval(self, writer):
         n_it = self.pipe['max_iter'] + 1 if self.pipe.get('iter') == 'iter' else 1
         results = {}
         self.metrics = {}
@@ -127,11 +148,15 @@ class YOND_Full:
             ds = self.dst_eval
             wp, bl = float(getattr(ds, 'wp', self.dst.get('wp', 1023))), float(getattr(ds, 'bl', self.dst.get('bl', 64)))
             sums = D.MetricSums(n_it)
+            device_ingest = hasattr(ds, 'raw_items') and not getattr(self.parser, 'host_ingest', False)
+            if hasattr(ds, 'raw_items'):
+                ds.raw_items = device_ingest                 # raw DN in the items, normalised on the device by the loader threads
             mine = D.shard_dataset(ds, self.rank, self.world)
             torch.cuda.synchronize()
             t0, t_path, npix = time.perf_counter(), 0.0, 0
             from .data import Prefetcher                     # loader threads read / convert / upload the frames ahead of the GPU
-            loader = Prefetcher(ds, mine, self.device, upload=('lr', 'hr'), depth=getattr(self.parser, 'prefetch', 4), workers=getattr(self.parser, 'loaders', 4))
+            loader = Prefetcher(ds, mine, self.device, upload=('lr', 'hr'), depth=getattr(self.parser, 'prefetch', 4), workers=getattr(self.parser, 'loaders', 4),
+                                ingest=device_ingest)
 
             def params_of(data):
                 p = dict(self.pipe)
@@ -153,6 +178,14 @@ class YOND_Full:
                 log(f"[rank {self.rank}] {data['name']}: " + (f"PSNR={psnrs[-1]:.2f}, SSIM={ssims[-1]:.4f}" if psnrs else "denoised (no reference frame)")
                     + f", K={res['params'][-1][0]:.3f}, sigma={res['params'][-1][1]:.3f}", self.logfile)
 
+            def deliver(k, data, res):
+                if callable(self.on_result):
+                    self.on_result(data['name'], res)
+                if writer is not None:                       # queued on this stream before the drivers reuse the buffer; written by the writer's threads
+                    writer.put(data['name'], res['raw_dns'][-1], (bl, wp, data.get('ratio', 1)),
+                               {'rounds': [(float(q[0]), float(q[1])) for q in res['params']]})
+                account(k, data, res)
+
             streamed = STREAM_EVAL and getattr(self.parser, 'stream', True) and not self.parser.verbose and P.stream_applies(self.pipe, self.pipe, self.biaslut)
             if streamed:
                 # pipeline.denoise_stream: the estimator of the next frame on a side stream, the network passes of consecutive frames on two lanes -- every
@@ -166,7 +199,7 @@ class YOND_Full:
                 t1 = time.perf_counter()
                 for res in P.denoise_stream(feed(), self.net, self.arch, self.pipe, device=self.device):
                     k, data = queue.pop(0)
-                    account(k, data, res)
+                    deliver(k, data, res)
                     npix += int(np.prod(tuple(data['lr'].shape)))
                 torch.cuda.synchronize()
                 t_path += time.perf_counter() - t1           # (includes what the loop waited for its loader threads)
@@ -175,7 +208,7 @@ class YOND_Full:
                     torch.cuda.synchronize()
                     t1 = time.perf_counter()
                     res = self.IterDenoise(data, {'p': params_of(data), 'img_id': k})
-                    account(k, data, res)
+                    deliver(k, data, res)
                     torch.cuda.synchronize()
                     t_path += time.perf_counter() - t1
                     npix += int(np.prod(tuple(data['lr'].shape)))

@@ -132,6 +132,9 @@ PROTOTYPES = {
     "yond_pack_vst_norm_chain_f32": [vp, i32, i32, vp, i32, i32, i32, i32, f64, vp, vp, i32, vp, vp],
     "yond_denorm_ivst_unpack_dev_f32": [vp, i32, i32, i32, i32, i32, i32, vp, i32, f64, vp, i32, vp],
     "yond_denorm_ivst_unpack_batch_dev_f32": [vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, f64, vp, i32, vp],
+    "yond_raw_ingest_u16": [vp, sz, f32, f32, f32, i32, vp, vp],
+    "yond_raw_ingest_f32": [vp, sz, f32, f32, f32, i32, vp, vp],
+    "yond_raw_emit_u16": [vp, sz, f32, f32, f32, i32, vp, vp, vp],
 }
 # experiment builds only (include/yond_hip_experiments.h): bound when the loaded library has them
 EXPERIMENT_PROTOTYPES = {

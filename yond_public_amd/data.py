@@ -120,12 +120,18 @@ def _levels(dirpath, args):
     return float(args['bl']), float(args['wp'])
 
 
+def _keep_raw(a):
+    """A raw frame as np.load returned it: uint16 and float32 are kept (the device ingests both), anything else becomes float32."""
+    return a if a.dtype in (np.uint16, np.float32) else a.astype(np.float32)
+
+
 class ELD_Full_Dataset:
     """data_process/yond_datasets.py:977-1067: <root_dir>/<camera>/scene-<1..10>/IMG_<id>.<suffix>, 3 ISOs x 4 ratios per
     scene, long-exposure references IMG_0001 / 0006 / 0011 / 0016; `change_eval_ratio(cam, ratio, iso_list)` selects the
     evaluated subset.  Items: 'lr' = (raw - bl) * ratio / (wp - bl), 'hr' = (raw - bl) / (wp - bl) (float32 Bayer frames),
     'name', 'ratio', 'ISO', 'wb', 'ccm' (identity without the raw file's metadata)."""
     SUFFIX = {'CanonEOS70D': 'CR2', 'CanonEOS700D': 'CR2', 'NikonD850': 'nef', 'SonyA7S2': 'ARW'}
+    raw_items = False        # True: items carry 'lr_raw' / 'hr_raw' (DN as loaded) + 'lr_levels' / 'hr_levels' = (bl, wp, ratio, clip), no 'lr' / 'hr'
 
     def __init__(self, args=None):
         self.args = {'root_dir': 'ELD/', 'ratio': 1, 'dstname': 'ELD', 'params': None, 'mode': 'eval', 'command': '',
@@ -164,6 +170,12 @@ class ELD_Full_Dataset:
         info = self.infos[idx]
         hr_raw = np.load(_npy_path(info['hr'])).reshape(self.H, self.W)
         lr_raw = np.load(_npy_path(info['lr'])).reshape(self.H, self.W)
+        if self.raw_items:                                       # normalised on the device (rawio.ingest; Prefetcher(ingest=True))
+            clip = bool(self.args['clip'])
+            return {'hr_raw': _keep_raw(hr_raw), 'lr_raw': _keep_raw(lr_raw), 'hr_levels': (self.bl, self.wp, 1, clip),
+                    'lr_levels': (self.bl, self.wp, info['ratio'], clip),
+                    'name': info['name'], 'ratio': info['ratio'], 'ISO': info['iso'], 'cfa': 'rggb',
+                    'wb': np.ones(4, np.float32), 'ccm': np.eye(3, dtype=np.float32), 'meta': None}
         data = {'hr': (hr_raw.astype(np.float32) - self.bl) / (self.wp - self.bl),
                 'lr': (lr_raw.astype(np.float32) - self.bl) * info['ratio'] / (self.wp - self.bl),
                 'name': info['name'], 'ratio': info['ratio'], 'ISO': info['iso'], 'cfa': 'rggb',
@@ -181,6 +193,7 @@ class LRID_Dataset:
         <root_dir>/<dstname>/<scene id>/gt.npy, x<ratio:02d>.npy [, meta.json {"wb": [4], "ccm": [3][3], "ExposureTime": s}]
     is scanned; `get_eval_id` keeps the reference's evaluation scenes (:938-950).  Items as the reference's: 'lr' scaled by
     the ratio, 'hr', 'name' = '<scene>_x<ratio:02d>', 'ratio', 'wb', 'ccm', 'ISO' = 6400, 'ExposureTime' in ms."""
+    raw_items = False        # as ELD_Full_Dataset.raw_items
 
     def __init__(self, args=None):
         self.args = {'root_dir': 'LRID/', 'suffix': 'dng', 'dgain': 1, 'dstname': ['indoor_x5'], 'camera_type': 'IMX686', 'params': None,
@@ -236,6 +249,12 @@ class LRID_Dataset:
         info = self.infos[idx]
         hr_raw = np.load(_npy_path(info['hr'])).reshape(self.H, self.W)
         lr_raw = np.load(_npy_path(info['lr'])).reshape(self.H, self.W)
+        if self.raw_items:
+            clip = bool(self.args['clip'])
+            return {'hr_raw': _keep_raw(hr_raw), 'lr_raw': _keep_raw(lr_raw), 'hr_levels': (self.bl, self.wp, 1, clip),
+                    'lr_levels': (self.bl, self.wp, self.ratio, clip),
+                    'name': f"{info['name']}_x{self.ratio:02d}", 'ratio': self.ratio, 'ccm': info['ccm'], 'wb': info['wb'], 'cfa': 'rggb',
+                    'ISO': self.iso, 'ExposureTime': info['ExposureTime'] * 1000, 'meta': None}
         data = {'hr': ((hr_raw.astype(np.float32) - self.bl) / (self.wp - self.bl)).astype(np.float32),
                 'lr': ((lr_raw.astype(np.float32) - self.bl) * self.ratio / (self.wp - self.bl)).astype(np.float32),
                 'name': f"{info['name']}_x{self.ratio:02d}", 'ratio': self.ratio, 'ccm': info['ccm'], 'wb': info['wb'], 'cfa': 'rggb',
@@ -249,6 +268,7 @@ class Any_Dataset:
     """README.md:38-47 'YOND_any': any directory of Bayer frames.  <root_dir>/*.npy (raw DN as the camera wrote them; a
     matching <root_dir>/gt/<same name>.npy is used as the reference frame when present); black / white level, ratio and clip
     from the runfile's dst section.  Items: 'lr' = (raw - bl) * ratio / (wp - bl), 'name', 'ratio'."""
+    raw_items = False        # as ELD_Full_Dataset.raw_items
 
     def __init__(self, args=None):
         self.args = {'root_dir': 'frames/', 'wp': 1023, 'bl': 64, 'clip': False, 'mode': 'eval', 'dstname': 'ANY'}
@@ -265,6 +285,14 @@ class Any_Dataset:
 
     def __getitem__(self, idx):
         f = self.files[idx]
+        if self.raw_items:
+            clip = bool(self.args['clip'])
+            data = {'lr_raw': _keep_raw(np.load(f)), 'lr_levels': (self.bl, self.wp, self.ratio, clip),
+                    'name': f"{os.path.splitext(os.path.basename(f))[0]}_x{self.ratio:02d}", 'ratio': self.ratio, 'cfa': 'rggb', 'meta': None}
+            g = os.path.join(self.args['root_dir'], 'gt', os.path.basename(f))
+            if os.path.exists(g):
+                data['hr_raw'], data['hr_levels'] = _keep_raw(np.load(g)), (self.bl, self.wp, 1, clip)
+            return data
         raw = np.load(f).astype(np.float32)
         data = {'lr': ((raw - self.bl) * self.ratio / (self.wp - self.bl)).astype(np.float32),
                 'name': f"{os.path.splitext(os.path.basename(f))[0]}_x{self.ratio:02d}", 'ratio': self.ratio, 'cfa': 'rggb', 'meta': None}
@@ -310,7 +338,7 @@ def item_sizes(ds):
 
 
 class _PinnedPool:
-    """Pinned staging buffers shared by a Prefetcher's workers: (key, shape) -> buffers with the event of their last upload.  A buffer is handed
+    """Pinned staging buffers shared by a Prefetcher's workers: (key, shape, dtype) -> buffers with the event of their last upload.  A buffer is handed
     out again once that event has completed; buffers of shapes that have not been used lately are dropped when the pool would grow past `budget`
     bytes (five SIDD frame sizes x per-worker double buffers had pinned ~2.5 GB of host memory)."""
 
@@ -318,9 +346,10 @@ class _PinnedPool:
         import threading
         self.lock, self.bufs, self.bytes, self.budget, self.clock = threading.Lock(), {}, 0, int(budget), 0
 
-    def take(self, key, shape):
+    def take(self, key, shape, dtype=None):
         import torch
-        pk = (key, tuple(shape))
+        dtype = dtype or torch.float32
+        pk = (key, tuple(shape), dtype)
         with self.lock:
             self.clock += 1
             lst = self.bufs.setdefault(pk, [])
@@ -328,7 +357,7 @@ class _PinnedPool:
                 if not b['busy'] and (b['ev'] is None or b['ev'].query()):
                     b['busy'], b['used'] = True, self.clock
                     return b
-            need = 4
+            need = torch.empty(0, dtype=dtype).element_size()
             for d in shape:
                 need *= int(d)
             if self.bytes + need > self.budget:                             # drop idle buffers of other shapes, least recently used first
@@ -337,9 +366,9 @@ class _PinnedPool:
                 for _, k2, b in idle:
                     if self.bytes + need <= self.budget:
                         break
-                    self.bufs[k2].remove(b)
-                    self.bytes -= b['t'].numel() * 4
-            b = {'t': torch.empty(tuple(shape), dtype=torch.float32).pin_memory(), 'ev': None, 'busy': True, 'used': self.clock}
+                    self.bufs[k2] = [q for q in self.bufs[k2] if q is not b]        # by identity: == on dicts compares their tensors
+                    self.bytes -= b['t'].numel() * b['t'].element_size()
+            b = {'t': torch.empty(tuple(shape), dtype=dtype).pin_memory(), 'ev': None, 'busy': True, 'used': self.clock}
             lst.append(b)
             self.bytes += need
             return b
@@ -355,14 +384,18 @@ class Prefetcher:
     a reused pinned buffer of a pool the workers share, sent on the worker's own copy stream; the consumer's current stream is made to wait
     for the copy's event, so no host synchronisation happens on the consumer's side).  Everything else in the item is passed through.  An
     exception in a worker is re-raised at the item it belongs to.
+    ingest=True: an item's `<key>_raw` array (raw DN, uint16 or float32: the datasets' raw_items mode) is staged in a pinned buffer of ITS OWN dtype,
+    uploaded on the worker's copy stream and normalised there by rawio.ingest with the item's `<key>_levels` = (bl, wp, ratio, clip) into
+    data[key]: 2 bytes per pixel cross the bus for a uint16 frame and the host does no arithmetic; the same event covers copy and kernel.
     The look-ahead is gated by POSITION: the worker of position p starts once p < consumed + depth.  (A counting semaphore lets workers that
     have already delivered take every permit for positions beyond the one the consumer is blocked on, while that position's worker starves.)"""
 
-    def __init__(self, ds, indices, device, upload=('lr', 'hr', 'lr_full'), depth=4, workers=4, pinned_budget=1 << 30):
+    def __init__(self, ds, indices, device, upload=('lr', 'hr', 'lr_full'), depth=4, workers=4, pinned_budget=1 << 30, ingest=False):
         import queue
         import threading
         import torch
         self.ds, self.indices, self.device, self.upload = ds, list(indices), torch.device(device), tuple(upload)
+        self.ingest = bool(ingest)
         self.workers = max(1, min(int(workers), len(self.indices) or 1))
         self.depth = max(self.workers, int(depth))
         self._slots = [queue.Queue(maxsize=1) for _ in self.indices]        # one-shot mailboxes, filled out of order, read in order
@@ -376,7 +409,12 @@ class Prefetcher:
 
     def _work(self, w):
         import torch
-        stream = torch.cuda.Stream(device=self.device) if self.device.type == 'cuda' else None
+        try:
+            stream = torch.cuda.Stream(device=self.device) if self.device.type == 'cuda' else None
+        except BaseException as e:                                          # noqa: BLE001 -- no usable device: every item of this worker says so
+            for pos in range(w, len(self.indices), self.workers):          # (a worker that died here left the consumer waiting for good)
+                self._slots[pos].put((self.indices[pos], None, None, e))
+            return
         for pos in range(w, len(self.indices), self.workers):
             with self._cv:
                 self._cv.wait_for(lambda: self._stop or pos < self._consumed + self.depth)
@@ -387,6 +425,23 @@ class Prefetcher:
                 data = dict(self.ds[k])
                 ev = None
                 for key in self.upload:
+                    raw = data.get(key + '_raw') if self.ingest else None
+                    if isinstance(raw, np.ndarray):
+                        from . import rawio
+                        bl, wp, ratio, clip = data[key + '_levels']
+                        del data[key + '_raw']
+                        if stream is None:
+                            data[key] = torch.from_numpy(rawio.ingest_host(raw, bl, wp, ratio, clip))
+                            continue
+                        raw = _keep_raw(raw)
+                        buf = self._pool.take(key + '_raw', raw.shape, torch.from_numpy(raw[:0]).dtype)
+                        buf['t'].numpy()[...] = raw
+                        with torch.cuda.stream(stream):
+                            data[key] = rawio.ingest(buf['t'].to(self.device, non_blocking=True), bl, wp, ratio, clip)
+                            ev = torch.cuda.Event()
+                            ev.record(stream)
+                        self._pool.give(buf, ev)
+                        continue
                     a = data.get(key)
                     if not isinstance(a, np.ndarray):
                         continue
