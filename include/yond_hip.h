@@ -523,7 +523,16 @@ int yond_denorm_ivst_unpack_batch_dev_f32(const float* net_out, int B, int Hp, i
  *   multiples of 32, NHWC); mode 0: 3x3 pad 1 (stride 1 / 2: Ho = ceil(H / stride)), 1: ConvTranspose2d 2x2 stride 2
  *   (Ho = 2H; taps dy*2+dx), 2: 1x1.
  * yond_colsum_f32: db[c] = sum_p dy[p][c].   yond_l1_loss_f32: loss_sum = sum |pred - target|, grad = sign(.) / n.
- * yond_adam_step_f32: torch.optim.Adam's single-tensor update (no weight decay / amsgrad), step = 1, 2, ... */
+ * yond_adam_step_f32: torch.optim.Adam's single-tensor update (no weight decay / amsgrad), step = 1, 2, ...
+ *   m' = m + w1 (g - m), v' = v b2 + (g g) w2, p' = p - step_size (m' / (sqrt(v') inv_bc2_sqrt + eps)): one float32 rounding per
+ *   operation, no FMA.  Every scalar is formed in float64 and rounded to float32 once, as torch rounds the doubles it hands to
+ *   lerp_ / addcmul_: w1 = float32(1 - beta1), w2 = float32(1 - beta2) (NOT 1.0f - float32(beta): 1.29e-5 apart for beta2 = 0.999),
+ *   b2 = float32(beta2), step_size = float32(lr / (1 - beta1^step)), inv_bc2_sqrt = float32(1 / sqrt(1 - beta2^step)), eps.  The
+ *   stored state is torch's up to the order of roundings (torch's kernels fuse each state line into one FMA): tests/train_model.py
+ *   has the float64 model and the per-element bounds.  Any element alignment.
+ * Losses with a NaN in pred or target: loss_sum becomes NaN (what TrainStep's third status word reports; the update is skipped); the
+ *   gradient at that element is 0 from yond_l1_loss_f32 (neither comparison holds) and NaN from yond_charbonnier_loss_f32; every
+ *   other element is unaffected.  pred == target (d = +-0) gives the L1 gradient +0.  The gradient scale is 1.0f / (float)n. */
 int yond_conv_wgrad_f32(const float* x, const float* dy, int N, int H, int W, int Cin, int Ho, int Wo, int Cout, int mode,
                         int stride, float* dw, void* stream);
 /* The same with a workspace: ws (device, yond_conv_wgrad_ws_bytes(...) bytes) takes the workgroups' partial sums, which a second
@@ -589,6 +598,10 @@ typedef struct YondFilmMlpDesc {
 } YondFilmMlpDesc;
 int yond_film_mlp_fwd_multi_f32(const YondFilmMlpDesc* d, int n, void* stream);
 int yond_film_mlp_bwd_multi_f32(const YondFilmMlpDesc* d, int n, void* stream);
+/* dx = dres + dz SiLU'(x), n (a multiple of 4) floats.  This entry and yond_silu_f32 move float4: every pointer must be 16-byte aligned
+ * (YOND_EINVAL otherwise; the other float4 kernels of this section -- colsum, film_silu, zero_interleave -- assume it).  SiLU and SiLU' are
+ * u s and s (1 + u (1 - s)) with s = 1 / (1 + expf(-u)): below u = -88.72284 expf overflows, s = 0 and both return -0 where the true value
+ * is below 3e-37 in magnitude. */
 int yond_silu_bwd_add_f32(const float* x, const float* dz, const float* dres, float* dx, size_t n, void* stream);
 /* y = SiLU(x), n (a multiple of 4) floats. */
 int yond_silu_f32(const float* x, float* y, size_t n, void* stream);

@@ -819,6 +819,10 @@ extern "C" int yond_film_mlp_bwd_multi_f32(const YondFilmMlpDesc* d, int n, void
     return YOND_OK;
 }
 
+// (the two SiLU entries below read and write float4: a pointer that is not 16-byte aligned is refused, not faulted on)
+template <typename... P>
+static bool aligned16(const P*... p) { return (((unsigned long long)p | ...) & 15ull) == 0; }
+
 // y = SiLU(x) (the operand of a guided block's first convolution, archs/modules.py:186-188)
 __global__ __launch_bounds__(256) void silu_kernel(const float4* __restrict__ x, float4* __restrict__ y, size_t n4) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
@@ -827,7 +831,7 @@ __global__ __launch_bounds__(256) void silu_kernel(const float4* __restrict__ x,
     }
 }
 extern "C" int yond_silu_f32(const float* x, float* y, size_t n, void* stream) {
-    if (!x || !y || n == 0 || n % 4) return YOND_EINVAL;
+    if (!x || !y || n == 0 || n % 4 || !aligned16(x, y)) return YOND_EINVAL;
     size_t nb = (n / 4 + 256 * 4 - 1) / (256 * 4);
     if (nb > 4096) nb = 4096;
     hipLaunchKernelGGL(silu_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (const float4*)x, (float4*)y, n / 4);
@@ -847,7 +851,7 @@ __global__ __launch_bounds__(256) void silu_bwd_add_kernel(const float4* __restr
     }
 }
 extern "C" int yond_silu_bwd_add_f32(const float* x, const float* dz, const float* dres, float* dx, size_t n, void* stream) {
-    if (!x || !dz || !dres || !dx || n == 0 || n % 4) return YOND_EINVAL;
+    if (!x || !dz || !dres || !dx || n == 0 || n % 4 || !aligned16(x, dz, dres, dx)) return YOND_EINVAL;
     size_t nb = (n / 4 + 256 * 4 - 1) / (256 * 4);
     if (nb > 4096) nb = 4096;
     hipLaunchKernelGGL(silu_bwd_add_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (const float4*)x, (const float4*)dz,
@@ -918,7 +922,7 @@ __global__ __launch_bounds__(256) void charbonnier_kernel(const float* __restric
     double acc = 0.0;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         const float d = __fsub_rn(pred[i], target[i]);
-        const float e = __fsqrt_rn(__fadd_rn(__fmul_rn(d, d), eps));
+        const float e = sqrtf(__fadd_rn(__fmul_rn(d, d), eps));       // (correctly rounded: see above adam_kernel)
         acc += (double)e;
         if (grad) {
             const float gu = __fdiv_rn(gscale, __fmul_rn(2.0f, e));
@@ -945,19 +949,26 @@ extern "C" int yond_charbonnier_loss_f32(const float* pred, const float* target,
     return YOND_OK;
 }
 
-// torch.optim.Adam.step (single tensor, no weight decay, no amsgrad), float32 state as torch keeps it:
-//   m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g g;  p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+// torch.optim.Adam.step (single tensor, no weight decay, no amsgrad), float32 state as torch keeps it up to the order of roundings (torch's
+// kernels fuse each state line into one FMA; here every operation rounds on its own):
+//   m = m + (1 - b1) (g - m);  v = b2 v + (1 - b2) g g;  p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+// What is rounded where: every scalar is formed in float64 on the host and rounded to float32 ONCE -- b2, omb1 = float32(1 - beta1),
+// omb2 = float32(1 - beta2), step_size = float32(lr / (1 - beta1^t)), inv_bc2_sqrt = float32(1 / sqrt(1 - beta2^t)), eps -- as torch
+// rounds the double scalars it hands to lerp_ / addcmul_.  (1.0f - float32(beta) is NOT float32(1 - beta): for beta2 = 0.999 it is
+// 0.0009999871, 1.29e-5 off, and exp_avg_sq would not be torch's.)  The kernel then takes one float32 rounding per operation, no FMA.
+// The square root is sqrtf(), which hipcc expands to the correctly rounded sequence (v_sqrt_f32 plus one correction step); __fsqrt_rn() is
+// NOT that in HIP: without OCML_BASIC_ROUNDED_OPERATIONS it is the native v_sqrt_f32, 1 ulp.  (__fdiv_rn is the IEEE division.)
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, size_t n, float b1, float b2, float step_size, float inv_bc2_sqrt,
-                                                   float eps) {
+                                                   float* __restrict__ v, size_t n, float omb1, float b2, float omb2, float step_size,
+                                                   float inv_bc2_sqrt, float eps) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         const float gi = g[i];
         // torch: exp_avg.lerp_(grad, 1 - beta1) = m + (1 - b1) (g - m); exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
-        const float mi = __fadd_rn(m[i], __fmul_rn(1.0f - b1, __fsub_rn(gi, m[i])));
-        const float vi = __fadd_rn(__fmul_rn(v[i], b2), __fmul_rn(__fmul_rn(gi, gi), 1.0f - b2));
+        const float mi = __fadd_rn(m[i], __fmul_rn(omb1, __fsub_rn(gi, m[i])));
+        const float vi = __fadd_rn(__fmul_rn(v[i], b2), __fmul_rn(__fmul_rn(gi, gi), omb2));
         m[i] = mi;
         v[i] = vi;
-        const float denom = __fadd_rn(__fmul_rn(__fsqrt_rn(vi), inv_bc2_sqrt), eps);
+        const float denom = __fadd_rn(__fmul_rn(sqrtf(vi), inv_bc2_sqrt), eps);
         p[i] = __fsub_rn(p[i], __fmul_rn(step_size, __fdiv_rn(mi, denom)));
     }
 }
@@ -967,17 +978,17 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
 // learning rate and step count; status (optional, three words): the update is skipped when bit 0 of any is set (a gradient, a weight left
 // fp16's range in the split-operand kernels; the caller's own word, e.g. a non-finite loss: the host lowers the loss scale and redoes the step).
 __global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                       float* __restrict__ v, size_t n, float b1, float b2, const float* __restrict__ hyp, float eps,
-                                                       const int* __restrict__ status) {
+                                                       float* __restrict__ v, size_t n, float omb1, float b2, float omb2, const float* __restrict__ hyp,
+                                                       float eps, const int* __restrict__ status) {
     if (status && ((status[0] | status[1] | status[2]) & 1)) return;
     const float step_size = hyp[0], inv_bc2_sqrt = hyp[1];
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         const float gi = g[i];
-        const float mi = __fadd_rn(m[i], __fmul_rn(1.0f - b1, __fsub_rn(gi, m[i])));
-        const float vi = __fadd_rn(__fmul_rn(v[i], b2), __fmul_rn(__fmul_rn(gi, gi), 1.0f - b2));
+        const float mi = __fadd_rn(m[i], __fmul_rn(omb1, __fsub_rn(gi, m[i])));
+        const float vi = __fadd_rn(__fmul_rn(v[i], b2), __fmul_rn(__fmul_rn(gi, gi), omb2));
         m[i] = mi;
         v[i] = vi;
-        const float denom = __fadd_rn(__fmul_rn(__fsqrt_rn(vi), inv_bc2_sqrt), eps);
+        const float denom = __fadd_rn(__fmul_rn(sqrtf(vi), inv_bc2_sqrt), eps);
         p[i] = __fsub_rn(p[i], __fmul_rn(step_size, __fdiv_rn(mi, denom)));
     }
 }
@@ -986,8 +997,8 @@ extern "C" int yond_adam_step_dev_f32(float* p, const float* g, float* m, float*
     if (!p || !g || !m || !v || !hyp || n == 0) return YOND_EINVAL;
     size_t nb = (n + 255) / 256;
     if (nb > 1024) nb = 1024;
-    hipLaunchKernelGGL(adam_dev_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, (float)beta1, (float)beta2, hyp,
-                       (float)eps, status);
+    hipLaunchKernelGGL(adam_dev_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, (float)(1.0 - beta1), (float)beta2,
+                       (float)(1.0 - beta2), hyp, (float)eps, status);
     YOND_LAUNCH_CHECK();
     return YOND_OK;
 }
@@ -998,8 +1009,8 @@ extern "C" int yond_adam_step_f32(float* p, const float* g, float* m, float* v, 
     const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
     size_t nb = (n + 255) / 256;
     if (nb > 1024) nb = 1024;
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, (float)beta1, (float)beta2,
-                       (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), (float)eps);
+    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, (float)(1.0 - beta1), (float)beta2,
+                       (float)(1.0 - beta2), (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), (float)eps);
     YOND_LAUNCH_CHECK();
     return YOND_OK;
 }

@@ -554,6 +554,8 @@ class _SiluRes(torch.autograd.Function):
         ctx.plan = plan
         if x.numel() % 4:
             return F.silu(x), x.view_as(x)
+        # (the kernel moves float4 and refuses a pointer that is not 16-byte aligned: a contiguous x that starts 1-3 elements into its
+        #  storage raises YondHipError here -- the step's tensors are whole allocations or slices at multiples of four floats)
         z = torch.empty_like(x)
         L.check(plan.lib.yond_silu_f32(L.ptr(x), L.ptr(z), x.numel(), L.stream()), "yond_silu_f32")
         return z, x.view_as(x)
@@ -918,7 +920,10 @@ class TrainStep:
 
     # -- the step as one hipGraph ------------------------------------------------------------------------------------
     def _hyp(self, t):
-        """The two scalars of Adam step t, in float64 as yond_adam_step_f32 computes them (csrc/train.hip)."""
+        """The two scalars of Adam step t, formed in float64 exactly as yond_adam_step_f32 forms them (csrc/train.hip) and rounded to
+        float32 once when they are copied into the graph's hyp buffer.  The kernels round every other scalar the same way -- beta2, eps and
+        the complements float32(1 - beta1), float32(1 - beta2), formed in float64 on the host (not 1.0f - float32(beta)) -- so the captured
+        and the eager step keep the same state as torch.optim.Adam up to the order of roundings."""
         return [self.lr / (1.0 - self.betas[0] ** t), 1.0 / math.sqrt(1.0 - self.betas[1] ** t)]
 
     def _flat_grad(self, S):
