@@ -657,6 +657,36 @@ int yond_img2raw_f32(const void* crops, size_t crops_len, int dtype, int H, int 
                      int B, int pattern, int clip, float* hr, float* lr, float* sigma, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * I2  Poisson-Gaussian noise on clean raw data (pgnoise.hip; 4 B in + 4 B out per element)
+ * The method's noise model, noisy = Poisson(x / beta1) * beta1 + N(0, beta2) (data_process/yond_datasets.py:720), for B items of
+ * n_per_item elements in one launch.  For item b and element i, x = clean[b * n + i], e = exposure, lambda = max(x, 0) * e / beta1:
+ *     noisy = (k * beta1) / e + min(x, 0) + sigma_n * z / e,     k ~ Poisson(lambda), z ~ N(0, 1) independent
+ * then clamped to [0, 1] when clip is 1.  e = 1, beta1 = K / scale, sigma_n = sigma / scale is the reference's training noise;
+ * e = 1 / ratio is a low-light exposure scaled back by ratio.
+ *   items      YondPGItem [B] (device); exposure must be finite and > 0, sigma_n finite and >= 0, beta1 finite
+ *   clean, noisy  float32 [B][n_per_item] (device), 4-byte aligned (views into tensors are fine), any n_per_item >= 1; either
+ *              disjoint or the same pointer (in place)
+ * Edges:  beta1 <= 0: no shot noise, noisy = x + sigma_n * z / e.  sigma_n == 0: no read noise, (noisy - min(x, 0)) * e / beta1 is
+ * an integer up to one rounding.  x < 0: noisy = x + read noise only (black-level-subtracted ground truth goes slightly negative).
+ * x NaN or +-inf: NaN; no other input gives a NaN or an infinity (where x * e / beta1 overflows float32 the shot term is x itself).
+ * Sampler (csrc/pgnoise_sampler.h): counter based -- Philox4x32-10 keyed by (key, slot), counter = (64-bit element index, draw
+ * number, a tag) -- so noisy[b][i] is a function of (items[b], i, clean[b][i]) alone: not of B, n_per_item, the launch geometry,
+ * neighbouring elements or the pointers' alignment.  k is exact in distribution, to the resolution of a 24-bit uniform and float32
+ * rounding of the acceptance test (~1e-6), for 0 <= lambda <= 2^23: inversion below lambda = 10 (at most 64 steps), the transformed
+ * rejection method PTRS (Hoermann 1993) from 10 to 2^23 (at most 64 attempts, then the normal value).  Above 2^23, where float32 no
+ * longer holds every count, k = max(0, rint(lambda + sqrt(lambda) * z')) with a second normal z'.  z is Box-Muller, |z| <= 5.77.
+ * Every loop has a fixed bound.  Refused (YOND_EINVAL, nothing launched): a null pointer, a pointer not 4-byte aligned, B < 1 or
+ * B > 65535, n_per_item == 0, clip outside {0, 1}. */
+typedef struct {
+    float beta1;          /* K / scale: the value of one count */
+    float sigma_n;        /* read-noise standard deviation, sigma / scale */
+    float exposure;       /* e */
+    uint32_t key, slot;   /* noise stream */
+} YondPGItem;             /* 20 bytes */
+int yond_pg_noise_f32(const float* clean, float* noisy, size_t n_per_item, int B, const YondPGItem* items /* device, [B] */, int clip,
+                      void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * E1 / E2  edge layers of the noise-estimation network EstUnet (estnet.hip; archs/Unet.py:474-611, archs/comp.py:35-126).  The
  * 3x3 layers between them, the pooling and the decoder's transposed 2x2 layers run on yond_conv2d_f32 / yond_maxpool2_f32.
  *   yond_est_conv_in_f32  3x3 on ONE full-resolution plane x [N][H][W], zero padding 1, + bias, ReLU -> dst [N][H][W][Cout].

@@ -126,6 +126,9 @@ class YOND_SIDD:
 
     def __init__(self, args=None):
         self.parser = YONDParser().parse(args)
+        if getattr(self.parser, 'synth_noise', None) is not None:
+            raise SystemExit("--synth-noise belongs to the full-frame drivers (YOND_any / YOND_ELD / YOND_LRID / YOND_DND): YOND_SIDD's block layout "
+                             "(32 blocks per image, the estimate on the full frame) is a different loop and has no synthetic-noise path")
         self.initialization()
 
     def initialization(self):
@@ -513,6 +516,11 @@ class YONDParser:
                        "writes the reference's cache npy/<method_name>/<k:03d>.npy, float32 [max_iter + 1][256][8192]")
         a.add_argument('--host-ingest', dest='host_ingest', action='store_true', default=False, help="full-frame drivers: normalise the raw frames on the host in "
                        "NumPy and upload float32 (the earlier path) instead of uploading the raw DN and normalising on the device")
+        from .pgnoise import synth_noise_arg
+        a.add_argument('--synth-noise', dest='synth_noise', type=synth_noise_arg, default=None, metavar='K,SIGMA', help="full-frame drivers: take every item's clean "
+                       "frame (hr if present, else lr) as the ground truth and make the noisy frame on the GPU, Poisson-Gaussian with system gain K and read "
+                       "noise SIGMA in DN; the log and the metrics gain the true level and the estimator's relative error per round, both in the estimate's units: "
+                       "DN of the frame the pipeline is handed, so a frame of ratio r reports ratio * K and ratio * SIGMA as the truth")
         return a.parse_args(args)
 
 

@@ -19,9 +19,17 @@ The two ends of a frame's trip are kernels (yond_public_amd/rawio.py): the datas
 float32), the loader threads upload them in that dtype and normalise on the device (`--host-ingest`: the NumPy expression on the
 host, as before); `--save dn16 | f32` writes every item's last round through a FrameWriter, as uint16 DN at the level of the frame
 the metrics were computed on (the digital gain kept) or as float32 in the [0, 1] scale, each with a JSON sidecar.
+
+`--synth-noise K,SIGMA` closes the loop for the blind estimator on a user's own frames: every item's clean frame (hr if present,
+else lr) is the ground truth, the noisy frame is made from it on the GPU (yond_public_amd/pgnoise.py: Poisson-Gaussian with system
+gain K and read noise SIGMA in DN of wp - bl, exposed at 1 / ratio, not clipped, noise key crc32(name)), and beside PSNR / SSIM the
+log and `metrics[name]` carry the true level and the estimator's relative error per round -- both in the estimate's own units, DN of
+the frame the pipeline is handed (digital gain included: ratio * K, ratio * SIGMA).  Without data the synthetic frames then
+hand out the clean frame only: no host Poisson draw in the loader threads.
 """
 import os
 import time
+import zlib
 
 import numpy as np
 import torch
@@ -30,6 +38,7 @@ import yaml
 from . import archs as _archs
 from . import data as _data
 from . import distributed as D
+from . import pgnoise as PG
 from . import pipeline as P
 from . import synthetic as S
 from .YOND_SIDD import YONDParser, load_estimators, log
@@ -38,10 +47,11 @@ STREAM_EVAL = True                 # eval(): frames through pipeline.denoise_str
 
 
 class SyntheticFrames:
-    """Stand-in when the runfile's root_dir holds no frames: low-light Poisson-Gaussian frames of the runfile's size."""
+    """Stand-in when the runfile's root_dir holds no frames: low-light Poisson-Gaussian frames of the runfile's size.
+    clean_only (the driver's --synth-noise): the clean frame alone, the driver makes the noise on the device."""
 
-    def __init__(self, n, H, W, K=2.0, sigma=8.0):
-        self.n, self.H, self.W, self.K, self.sigma, self.ratio = n, H, W, K, sigma, 1
+    def __init__(self, n, H, W, K=2.0, sigma=8.0, clean_only=False):
+        self.n, self.H, self.W, self.K, self.sigma, self.ratio, self.clean_only = n, H, W, K, sigma, 1, bool(clean_only)
 
     def __len__(self):
         return self.n
@@ -52,6 +62,9 @@ class SyntheticFrames:
     def __getitem__(self, k):
         rng = np.random.default_rng(4000 + k)
         clean = (S.synth_clean(self.H, self.W) * (0.6 / self.ratio)).astype(np.float32)       # exposure 1 / ratio ...
+        if self.clean_only:
+            return {'hr': (clean * self.ratio).astype(np.float32), 'name': f'synthetic_{k:03d}_x{self.ratio:02d}', 'ratio': self.ratio,
+                    'cfa': 'rggb', 'meta': None}
         noisy = (rng.poisson(clean * 959.0 / self.K) * self.K + rng.normal(0.0, self.sigma, clean.shape)) / 959.0
         return {'lr': (noisy * self.ratio).astype(np.float32), 'hr': (clean * self.ratio).astype(np.float32),   # ... digital gain = ratio
                 'name': f'synthetic_{k:03d}_x{self.ratio:02d}', 'ratio': self.ratio, 'cfa': 'rggb', 'meta': None}
@@ -70,6 +83,7 @@ class YOND_Full:
             raise SystemExit("the full-frame drivers need an MI355X: the HIP path has no CPU fallback")
         self.device = torch.device('cuda', self.local_rank)
         torch.cuda.set_device(self.device)
+        self.synth_noise = getattr(self.parser, 'synth_noise', None)    # (K, sigma) in DN, or None
         self.arch, self.pipe = self.args['arch'], dict(self.args['pipeline'])
         if self.pipe.get('bias_corr') == 'none':
             self.pipe['bias_corr'] = None
@@ -107,7 +121,21 @@ class YOND_Full:
             if len(ds) or cls != 'Any_Dataset':
                 self.dst_eval = ds
         if self.dst_eval is None or (len(self.dst_eval) == 0 and cls == 'Any_Dataset'):
-            self.dst_eval = SyntheticFrames(self.parser.synthetic, int(self.dst.get('H', 3472)), int(self.dst.get('W', 4624)))
+            self.dst_eval = SyntheticFrames(self.parser.synthetic, int(self.dst.get('H', 3472)), int(self.dst.get('W', 4624)),
+                                            clean_only=self.synth_noise is not None)
+
+    def synthesise(self, data, wp, bl):
+        """--synth-noise: the item's clean frame becomes its ground truth and a noisy frame made from it on the current stream its
+        input (one yond_pg_noise_f32 launch; the same name gives the same noise)."""
+        K, sigma = self.synth_noise
+        clean = data['hr'] if data.get('hr') is not None else data['lr']
+        if not isinstance(clean, torch.Tensor):
+            clean = torch.from_numpy(np.ascontiguousarray(clean, np.float32))
+        clean = clean.to(self.device, torch.float32).contiguous()
+        data['hr'] = clean
+        data['lr'] = PG.add_pg_noise(clean, K, sigma, wp - bl, zlib.crc32(str(data['name']).encode()), [0],
+                                     exposure=1.0 / float(data.get('ratio', 1)))
+        return data
 
     def IterDenoise(self, data, params):
         return P.IterDenoise(data['lr'], self.net, self.arch, self.pipe, p=params['p'], device=self.device,
@@ -148,6 +176,7 @@ class YOND_Full:
             ds = self.dst_eval
             wp, bl = float(getattr(ds, 'wp', self.dst.get('wp', 1023))), float(getattr(ds, 'bl', self.dst.get('bl', 64)))
             sums = D.MetricSums(n_it)
+            rel_sums = [0.0] * (4 * n_it)                        # --synth-noise: per round [sum, frames] of K's and of sigma's relative error
             device_ingest = hasattr(ds, 'raw_items') and not getattr(self.parser, 'host_ingest', False)
             if hasattr(ds, 'raw_items'):
                 ds.raw_items = device_ingest                 # raw DN in the items, normalised on the device by the loader threads
@@ -175,8 +204,24 @@ class YOND_Full:
                         ssims.append(float(np.mean(ss)))
                     sums.update(psnrs, ssims)
                 self.metrics[data['name']] = {'psnr': psnrs, 'ssim': ssims, 'reg': res['regs']}
+                true = ""
+                if self.synth_noise is not None:
+                    # the pipeline's (K, sigma) are DN of the frame it is handed (YOND_SIDD.py:356 scales by wp - bl), digital gain
+                    # included: a frame exposed at 1 / ratio and scaled back by ratio carries ratio * K and ratio * SIGMA
+                    ratio = float(data.get('ratio', 1))
+                    K, sigma = self.synth_noise[0] * ratio, self.synth_noise[1] * ratio
+                    # (SIGMA = 0, pure shot noise, has no relative error: None there, and no share in the sweep's mean)
+                    rel = [(float(abs(q[0] - K) / K), float(abs(q[1] - sigma) / sigma) if sigma > 0 else None) for q in res['params']]
+                    self.metrics[data['name']].update(true=(K, sigma), rel_err=rel)
+                    for it, (rk, rs) in enumerate(rel[:n_it]):
+                        rel_sums[4 * it] += rk
+                        rel_sums[4 * it + 1] += 1
+                        if rs is not None:
+                            rel_sums[4 * it + 2] += rs
+                            rel_sums[4 * it + 3] += 1
+                    true = f", true K={K:.3f}, sigma={sigma:.3f}"
                 log(f"[rank {self.rank}] {data['name']}: " + (f"PSNR={psnrs[-1]:.2f}, SSIM={ssims[-1]:.4f}" if psnrs else "denoised (no reference frame)")
-                    + f", K={res['params'][-1][0]:.3f}, sigma={res['params'][-1][1]:.3f}", self.logfile)
+                    + f", K={res['params'][-1][0]:.3f}, sigma={res['params'][-1][1]:.3f}" + true, self.logfile)
 
             def deliver(k, data, res):
                 if callable(self.on_result):
@@ -194,6 +239,8 @@ class YOND_Full:
 
                 def feed():
                     for k, data in loader:
+                        if self.synth_noise is not None:
+                            data = self.synthesise(data, wp, bl)
                         queue.append((k, data))
                         yield data['lr'], params_of(data)
                 t1 = time.perf_counter()
@@ -205,6 +252,8 @@ class YOND_Full:
                 t_path += time.perf_counter() - t1           # (includes what the loop waited for its loader threads)
             else:
                 for k, data in loader:
+                    if self.synth_noise is not None:
+                        data = self.synthesise(data, wp, bl)
                     torch.cuda.synchronize()
                     t1 = time.perf_counter()
                     res = self.IterDenoise(data, {'p': params_of(data), 'img_id': k})
@@ -215,12 +264,22 @@ class YOND_Full:
             torch.cuda.synchronize()
             dt = D.max_over_ranks(time.perf_counter() - t0, self.device)
             red = sums.reduce(self.device)
+            if self.synth_noise is not None:
+                rel = D.sum_over_ranks(rel_sums, self.device)
+                for it in range(n_it):
+                    if rel[4 * it + 1]:
+                        red[f'rel_err_K_iter{it}'] = rel[4 * it] / rel[4 * it + 1]
+                    if rel[4 * it + 3]:
+                        red[f'rel_err_sigma_iter{it}'] = rel[4 * it + 2] / rel[4 * it + 3]
             results[label] = red
             if self.rank == 0:
                 log(f'{self.method_name} [{label}]: {len(ds)} frames', self.logfile)
                 if red['count']:
                     for it in range(n_it):
-                        log(f"Iter{it}: PSNR={red[f'psnr_iter{it}']:.2f}, SSIM={red[f'ssim_iter{it}']:.4f}", self.logfile)
+                        log(f"Iter{it}: PSNR={red[f'psnr_iter{it}']:.2f}, SSIM={red[f'ssim_iter{it}']:.4f}"
+                            + (f", mean |K_est - K| / K = {red[f'rel_err_K_iter{it}']:.4f}" if f'rel_err_K_iter{it}' in red else "")
+                            + (f", mean |sigma_est - sigma| / sigma = {red[f'rel_err_sigma_iter{it}']:.4f}" if f'rel_err_sigma_iter{it}' in red else ""),
+                            self.logfile)
                     log(f"Iter_last: PSNR={red['psnr_last']:.2f}, SSIM={red['ssim_last']:.4f}", self.logfile)
                 log(f"{len(ds)} frames on {self.world} GPU(s) in {dt:.2f} s (rank 0: {t_path / max(len(mine), 1) * 1e3:.1f} ms per frame in "
                     + ("denoise_stream + metrics, waits for the loader threads included" if streamed else "IterDenoise + metrics")

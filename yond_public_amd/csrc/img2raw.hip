@@ -5,36 +5,9 @@
 // index maps), looks its 3 levels up in the transfer curve (LDS for uint8, L2-resident global memory for uint16), applies the CCM
 // and the gain mask and keeps the one channel its mosaic site needs.  grid = (ceil(h'w' / 256), B).
 #include "common.h"
+#include "philox.h"
 
 #define I2R_T 256
-
-struct Philox4 { uint32_t v[4]; };
-
-__device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t lo0 = 0xD2511F53u * c0, hi0 = __umulhi(0xD2511F53u, c0);
-        const uint32_t lo1 = 0xCD9E8D57u * c2, hi1 = __umulhi(0xCD9E8D57u, c2);
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return Philox4{{c0, c1, c2, c3}};
-}
-
-// Box-Muller on two 32-bit words: u1 in (0, 1] (24 bits), u2 in [0, 1)
-__device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& z0, float& z1) {
-    const float u1 = (float)((a >> 8) + 1u) * 5.9604644775390625e-8f;
-    const float u2 = (float)(b >> 8) * 5.9604644775390625e-8f;
-    const float r = sqrtf(-2.0f * logf(u1));
-    float s, c;
-    sincospif(2.0f * u2, &s, &c);
-    z0 = r * c;
-    z1 = r * s;
-}
 
 template <typename T>
 __global__ __launch_bounds__(I2R_T) void img2raw_kernel(const T* __restrict__ crops, size_t crops_len, int H, int W,

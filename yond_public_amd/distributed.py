@@ -158,6 +158,18 @@ def max_over_ranks(x, device=None):
     return float(x)
 
 
+def sum_over_ranks(values, device=None):
+    """The element-wise sum of a list of floats over the ranks (one all-reduce; the list itself without a process group)."""
+    if _active():
+        t = torch.tensor(list(values), dtype=torch.float64)
+        if dist.get_backend() == "nccl":
+            t = t.to(device if device is not None else torch.device("cuda", torch.cuda.current_device()))
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        STATS["all_reduce"] += 1
+        return [float(v) for v in t.cpu()]
+    return [float(v) for v in values]
+
+
 def gather_over_ranks(x, device=None):
     """Every rank's value of the scalar x, in rank order (all_gather; [x] without a process group)."""
     if _active():

@@ -21,6 +21,10 @@ reference's layout) holds one of two kinds of patch.
   - patches ALREADY packed raw, each (4, h, w) or (h, w, 4) float in [0, 1], with the reference's noise model on top on the host
     (yond_datasets.py:308-320: sigma log-uniform in [sigma_min, sigma_max] / 255 when training, the fixed `dst_eval.sigma` with a
     per-index seed otherwise; Bayer-pattern augmentation by rotating the mosaic, :296-303).
+DIV2K_PG_Dataset (yond_datasets.py:661-764) takes sRGB crops only and puts signal-dependent noise on them: (K, sigma) per training
+item from the reference's camera-noise prior, noisy = Poisson(x / beta1) beta1 + N(0, beta2) in one more launch
+(yond_public_amd/pgnoise.py, csrc/pgnoise.hip); every evaluation item gets `dst_eval.K` / `dst_eval.sigma_dn` (or `--synth-noise
+K,SIGMA`), else the prior's draw on RandomState(0).  Its `command: est` branch and guided architectures are refused.
 A directory mixing the two is refused before the first step.  Without data the trainer draws seeded synthetic patches so that
 the loop can be exercised and timed.  Plots, FastISP previews (the function itself: utils/isp_ops.FastISP) and the consistency branch (`command: consistency`) are not wired in.
 """
@@ -38,6 +42,7 @@ import yaml
 from . import archs as _archs
 from . import distributed as D
 from . import img2raw as I
+from . import pgnoise as PG
 from . import synthetic as S
 from . import train as T
 from .YOND_SIDD import log
@@ -152,6 +157,37 @@ class DIV2K_Img2Raw_Dataset(RGB_Img2Raw_Dataset):
         return ref if not _npy_files(d) and _npy_files(ref) else d
 
 
+class DIV2K_PG_Dataset(DIV2K_Img2Raw_Dataset):
+    """yond_datasets.py:661-764: sRGB crop -> unprocess -> mosaic -> Poisson-Gaussian noise with (K, sigma) from a camera-noise
+    prior (pgnoise.sample_pg_params).  Device path only (pgnoise.PGSource): the items are never made on the host.  The reference
+    draws ONE unseeded (K, sigma) at construction for all evaluation items; here they are the runfile's `K` / `sigma_dn` (both in DN
+    of wp - bl = 959) or the prior's draw on RandomState(0)."""
+
+    def __init__(self, args, synthetic=0):
+        if 'est' in str(args.get('command', '')):
+            raise NotImplementedError("DIV2K_PG_Dataset with `command: est` (the blur / local-std feature stacks that train the noise "
+                                      "estimator, yond_datasets.py:721-751) is not built: only the denoiser's (lr, hr) pairs are")
+        super().__init__(args, synthetic)
+        if not self.datapath or I.crop_kind(self.datapath) != 'srgb':
+            raise ValueError(f"DIV2K_PG_Dataset synthesises its raw pairs from sRGB crops, (H, W, 3) uint8 / uint16 .npy files: "
+                             f"{self._data_dir()} holds " + ("packed raw patches" if self.datapath else "none (and has no synthetic stand-in)"))
+        self.noise_params = dict(PG.NOISE_PRIOR)
+        self.p = PG.sample_pg_params(np.random.RandomState(0))
+        if 'K' in self.args or 'sigma_dn' in self.args:
+            if not ('K' in self.args and 'sigma_dn' in self.args):
+                raise ValueError("DIV2K_PG_Dataset: give both `K` and `sigma_dn` (DN) or neither")
+            self.set_noise(self.args['K'], self.args['sigma_dn'])
+
+    def set_noise(self, K, sigma):
+        """The (K, sigma) in DN of every evaluation item."""
+        K, sigma = PG.synth_noise_arg(f"{K},{sigma}")
+        scale = self.p['scale']
+        self.p = dict(self.p, K=K, sigma=sigma, beta1=K / scale, beta2=(sigma / scale) ** 2)
+
+    def __getitem__(self, idx, rng=None):
+        raise NotImplementedError("DIV2K_PG_Dataset items are made on the GPU (pgnoise.PGSource), not on the host")
+
+
 def _npy_files(d):
     return sorted(str(p) for p in Path(d).glob('*.npy')) if os.path.isdir(d) else []
 
@@ -161,6 +197,8 @@ def img2raw_source(ds, device):
     patches.  A directory mixing both kinds raises here, before any step."""
     if not ds.datapath or I.crop_kind(ds.datapath) != 'srgb':
         return None
+    if isinstance(ds, DIV2K_PG_Dataset):
+        return PG.PGSource(ds.datapath, ds.args, device, ds.p)
     return I.Img2RawSource(ds.datapath, ds.args, device, div2k=isinstance(ds, DIV2K_Img2Raw_Dataset))
 
 
@@ -230,6 +268,8 @@ class AWGN_Parser:
         # not reference flags:
         p.add_argument('--synthetic', type=int, default=0, help="train / evaluate on N synthetic patches when root_dir holds none")
         p.add_argument('--epochs', type=int, default=None, help="stop after this many epochs (default: hyper.stop_epoch)")
+        p.add_argument('--synth-noise', dest='synth_noise', type=PG.synth_noise_arg, default=None, metavar='K,SIGMA',
+                       help="DIV2K_PG_Dataset: system gain K and read noise SIGMA (DN) of every evaluation item, instead of the runfile's")
         return p.parse_args(args)
 
 
@@ -263,6 +303,13 @@ class AWGN_Trainer:
     def initialization(self):
         with open(self.parser.runfile, 'r', encoding='utf-8') as f:
             self.args = yaml.load(f.read(), Loader=yaml.FullLoader)
+        pg = [s for s in ('dst_train', 'dst_eval') if self.args[s]['dataset'] == 'DIV2K_PG_Dataset']
+        if pg and 'guided' in self.args['arch']:               # before a device, a dataset or a network exists
+            raise ValueError(f"{self.args['arch']['name']} is a guided architecture and {pg[0]} is DIV2K_PG_Dataset: the reference would hand the "
+                             "net the read noise sigma in DN as its AWGN guidance t, which means nothing -- train an unguided net on this dataset")
+        if self.parser.synth_noise is not None and self.args['dst_eval']['dataset'] != 'DIV2K_PG_Dataset':
+            raise SystemExit("--synth-noise sets the evaluation noise of DIV2K_PG_Dataset; "
+                             f"this runfile's dst_eval is {self.args['dst_eval']['dataset']}")
         self.mode = self.args['mode'] if self.parser.mode is None else self.parser.mode
         if 'clip' not in self.args['dst']:
             self.args['dst']['clip'] = False
@@ -299,6 +346,8 @@ class AWGN_Trainer:
         self.dst = self.args[f'dst_{mode}']
         self.dstname = self.dst['dstname']
         self.dst_eval = globals()[self.dst['dataset']](self.dst, self.parser.synthetic)
+        if self.parser.synth_noise is not None and isinstance(self.dst_eval, DIV2K_PG_Dataset):
+            self.dst_eval.set_noise(*self.parser.synth_noise)
         self.src_eval = img2raw_source(self.dst_eval, self.device)
 
     # -- trainer_AWGN.py:347-368 -----------------------------------------------------------------------------------------------
@@ -382,7 +431,7 @@ class AWGN_Trainer:
                 data = self.dst_eval[k]
                 imgs_lr, imgs_hr, sigma = self.preprocess({'lr': data['lr'][None], 'hr': data['hr'][None], 'sigma': data['sigma']},
                                                           mode='eval', preprocess=False)
-            name = data['name'] + f'_sig{int(sigma.item() * 255)}'
+            name = data['name'] + (f"_K{float(data['K']):.3g}" if 'K' in data else f'_sig{int(sigma.item() * 255)}')
             pad = imgs_lr.shape[-1] % 16 != 0                  # :220-225 (the reference calls a guided net without sigma there)
             x = torch.nn.functional.pad(imgs_lr, (4, 4, 4, 4), mode='reflect') if pad else imgs_lr
             imgs_dn = self.net(x, sigma) if guided else self.net(x)
@@ -426,7 +475,12 @@ def main(argv=None):
             trainer.net = load_weights(trainer.net, torch.load(best, map_location=trainer.device), by_name=True)
         if 'eval' in trainer.mode and trainer.rank == 0:
             trainer.change_eval_dst('eval')
-            for sigma in trainer.args['dst_test']['sigma_list']:
+            pg = isinstance(trainer.dst_eval, DIV2K_PG_Dataset)
+            if pg:                                                      # one fixed (K, sigma): one pass, sigma_list is not read
+                log(f"PG Dataset: K={trainer.dst_eval.p['K']:.3f}, sigma={trainer.dst_eval.p['sigma']:.3f} DN", log=trainer.logfile)
+                out['metrics_pg'] = dict(trainer.eval(-1))
+                out['psnr_pg'], out['ssim_pg'] = trainer.eval_psnr.avg, trainer.eval_ssim.avg
+            for sigma in ([] if pg else trainer.args['dst_test']['sigma_list']):
                 log(f'AWGN Datasets: sigma={sigma}', log=trainer.logfile)
                 trainer.dst_eval.sigma = sigma / 255.
                 out[f'metrics_sig{sigma}'] = dict(trainer.eval(-1))
