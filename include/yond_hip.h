@@ -687,7 +687,66 @@ int yond_pg_noise_f32(const float* clean, float* noisy, size_t n_per_item, int B
                       void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * E1 / E2  edge layers of the noise-estimation network EstUnet (estnet.hip; archs/Unet.py:474-611, archs/comp.py:35-126).  The
+ * I3  Camera noise on clean raw data (camnoise.hip; 4 B in + 4 B out per element, bound by the sampler's arithmetic)
+ * The low-light sensor model of data_process/process.py:631-671 (generate_noisy_obs, noise codes p g r q d): what a sensor adds to
+ * Poisson-Gaussian noise at exposure ratios of 100-300 -- heavy-tailed (Tukey-lambda) read noise, row noise, quantisation noise and a
+ * per-channel dark bias -- for B items of n_per_item elements in one launch.  For item b and element i, x = clean[b * n + i],
+ * e = exposure, m = mfm, y = max(x, 0) * e:
+ *     shot   Poisson (flag bit 0):     k * beta1 / m,  k ~ Poisson(m * y / beta1)
+ *            Gaussian approximation:   y + z_s * sqrt(max(y / beta1, 1e-10)) * beta1 / m           (process.py:646-648)
+ *     read   Tukey-lambda (bit 1):     (sig_read / m) * T,  T ~ Tukey-lambda(lam) of scale 1 (sig_read is the SCALE, not the deviation)
+ *            Gaussian:                 (sig_read / m) * z
+ *     row    (sig_row / m) * z_row, one z_row per row
+ *     q      q_step * u_q, u_q uniform on (-0.5, 0.5); NOT divided by m, as in the reference
+ *     bias   bias[c], c the element's CFA channel
+ *     noisy = clip(shot + read + row + q + bias + min(x, 0) * e) / e,  clip to [clip_lo, clip_hi] when flag bit 2 is set, else none:
+ * the clip stands BEFORE the division by e, as process.py:667-669 has it.  (The kernel divides each term by e and clips to
+ * [clip_lo / e, clip_hi / e]: the same set of values, and the order of yond_pg_noise_f32's sum.)
+ * Degenerate case: flags = Poisson (| clip), sig_row = q_step = 0, bias 0, mfm = 1 gives yond_pg_noise_f32's output BIT FOR BIT for
+ * the same (beta1, sig_read, exposure, key, slot) -- with the clip off, and with clip [0, 1] where e = 1.
+ * Geometry (what "row" and "channel" mean):
+ *   layout 0   packed planar [4][h][row_len]: row = i / row_len (rows of different channels are independent, the reference's (c, h, 1)
+ *              draw), channel = i / (n_per_item / 4)
+ *   layout 1   Bayer [H][row_len]: row = the sensor row i / row_len, channel = 2 * (row & 1) + (col & 1), as yond_bayer2rggb_f32
+ *   row_len 0  no geometry: the caller states that no item has row noise or a bias (yond_public_amd/camnoise.py checks its items; the
+ *              items live on the device, this entry point cannot).  An item that has them all the same is ONE row of channel 0.
+ *   items      YondCamItem [B] (device); exposure and mfm finite and > 0, sig_* and q_step finite and >= 0, lam finite and > -0.5,
+ *              beta1, bias and the clip bounds finite
+ *   clean, noisy  float32 [B][n_per_item] (device), 4-byte aligned, any n_per_item >= 1 the geometry divides; disjoint or the same
+ *              pointer (in place)
+ * Edges:  beta1 <= 0: no shot noise, the shot term is y.  x < 0 carries through: noisy = x + (the other terms) / e.  x NaN or
+ * +-inf: NaN; no other input gives a NaN or an infinity.
+ * Sampler (csrc/camnoise_sampler.h): counter based on Philox4x32-10 keyed by (key, slot).  k and z are pg_draw's of
+ * csrc/pgnoise_sampler.h, same counter and tag; T, u_q and z_s come from one draw under a second tag, counted by the element index;
+ * z_row from a third tag with the ROW index in the counter: a function of (key, slot, row) alone.  So noisy[b][i] is a function of
+ * (items[b], i, clean[b][i], layout, row_len, n_per_item) and not of B, the launch geometry, neighbours or alignment.
+ * T = -+Q_lam(u), Q_lam(u) = (u^lam - (1 - u)^lam) / lam (scipy.stats.tukeylambda.ppf), u uniform on [2^-33, 1/2] with 32 bits and a
+ * sign bit: the tail is truncated at |T| <= |Q_lam(2^-33)| -- 1468 at lam = -0.26, 22.9 at lam = 0, 8.85 at lam = 0.102 -- cutting
+ * off a mass of 2^-32.  z, z_s, z_row are Box-Muller, |z| <= 5.77.  Every loop has a fixed bound.
+ * Refused (YOND_EINVAL, nothing launched): a null pointer, a pointer not 4-byte aligned, B < 1 or B > 65535, n_per_item == 0, a
+ * layout outside {0, 1}, row_len < 0, and a row_len > 0 that does not divide the plane n_per_item / 4 (layout 0; n_per_item must
+ * then be a multiple of 4) or n_per_item (layout 1), or that comes with n_per_item >= 2^32 (rows and columns are 32-bit). */
+#define YOND_CAM_POISSON 1u   /* flags bit 0: Poisson shot noise (else the Gaussian approximation) */
+#define YOND_CAM_TUKEY 2u     /* flags bit 1: Tukey-lambda read noise (else Gaussian) */
+#define YOND_CAM_CLIP 4u      /* flags bit 2: clip to [clip_lo, clip_hi] before the division by the exposure */
+typedef struct {
+    float beta1;            /* K / scale */
+    float sig_read;         /* Gaussian std, or Tukey-lambda SCALE (not std), / scale */
+    float lam;              /* Tukey-lambda shape */
+    float sig_row;          /* / scale */
+    float q_step;           /* width of the uniform quantisation noise / scale: 1 / scale is the reference's +-0.5 DN; 0 = off */
+    float bias[4];          /* per CFA channel, / scale */
+    float exposure;         /* e = 1 / ratio */
+    float mfm;              /* sqrt(MultiFrameMean) */
+    float clip_lo, clip_hi;
+    uint32_t flags;         /* YOND_CAM_* */
+    uint32_t key, slot;     /* noise stream */
+} YondCamItem;              /* 64 bytes */
+int yond_camera_noise_f32(const float* clean, float* noisy, size_t n_per_item, int B, const YondCamItem* items /* device, [B] */,
+                          int layout, int row_len, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * E1 / E2 edge layers of the noise-estimation network EstUnet (estnet.hip; archs/Unet.py:474-611, archs/comp.py:35-126).  The
  * 3x3 layers between them, the pooling and the decoder's transposed 2x2 layers run on yond_conv2d_f32 / yond_maxpool2_f32.
  *   yond_est_conv_in_f32  3x3 on ONE full-resolution plane x [N][H][W], zero padding 1, + bias, ReLU -> dst [N][H][W][Cout].
  *                         w [Cout][9] and bias [Cout] on the device, zero-padded to Cout (a multiple of 32, <= 1024).

@@ -129,6 +129,9 @@ class YOND_SIDD:
         if getattr(self.parser, 'synth_noise', None) is not None:
             raise SystemExit("--synth-noise belongs to the full-frame drivers (YOND_any / YOND_ELD / YOND_LRID / YOND_DND): YOND_SIDD's block layout "
                              "(32 blocks per image, the estimate on the full frame) is a different loop and has no synthetic-noise path")
+        if getattr(self.parser, 'camera_noise', None) is not None:
+            raise SystemExit("--camera-noise belongs to the full-frame drivers (YOND_any / YOND_ELD / YOND_LRID / YOND_DND): YOND_SIDD's block layout "
+                             "(32 blocks per image, the estimate on the full frame) is a different loop and has no synthetic-noise path")
         self.initialization()
 
     def initialization(self):
@@ -521,6 +524,13 @@ class YONDParser:
                        "frame (hr if present, else lr) as the ground truth and make the noisy frame on the GPU, Poisson-Gaussian with system gain K and read "
                        "noise SIGMA in DN; the log and the metrics gain the true level and the estimator's relative error per round, both in the estimate's units: "
                        "DN of the frame the pipeline is handed, so a frame of ratio r reports ratio * K and ratio * SIGMA as the truth")
+        from .camnoise import camera_noise_arg
+        a.add_argument('--camera-noise', dest='camera_noise', type=camera_noise_arg, default=None, metavar='SPEC', help="full-frame drivers: as --synth-noise, "
+                       "with the low-light camera noise model instead of Poisson-Gaussian: SPEC is a comma list of key=value in DN at capture (before the "
+                       "ratio), e.g. code=pgrq,K=0.22,sigTL=0.76,sigGs=1.26,sigR=0.23,lam=-0.026; code holds the reference's letters (p Poisson shot, "
+                       "g Tukey-lambda read noise of scale sigTL and shape lam -- without g Gaussian read noise sigGs --, r row noise sigR, q quantisation, "
+                       "d dark bias, b shot only); optional bias=b0/b1/b2/b3, mfm=, clip=none|01|sensor.  The truth reported is the Poisson-Gaussian "
+                       "level of the same variance, ratio * K and ratio * sigma_eff.  Not together with --synth-noise")
         return a.parse_args(args)
 
 

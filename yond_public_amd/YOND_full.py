@@ -26,6 +26,13 @@ gain K and read noise SIGMA in DN of wp - bl, exposed at 1 / ratio, not clipped,
 log and `metrics[name]` carry the true level and the estimator's relative error per round -- both in the estimate's own units, DN of
 the frame the pipeline is handed (digital gain included: ratio * K, ratio * SIGMA).  Without data the synthetic frames then
 hand out the clean frame only: no host Poisson draw in the loader threads.
+
+`--camera-noise SPEC` does the same with the low-light camera model (yond_public_amd/camnoise.py: Poisson or Gaussian shot noise,
+Tukey-lambda or Gaussian read noise, row noise, quantisation, dark bias; SPEC in DN at capture, e.g.
+code=pgrq,K=0.22,sigTL=0.76,sigGs=1.26,sigR=0.23,lam=-0.026): how far do the Poisson-Gaussian line fit and the denoiser drift under
+banding and heavy tails.  The truth it reports is the Poisson-Gaussian level with the model's variance (camnoise.effective_pg:
+ratio * K, ratio * sigma_eff); the dark bias is a mean offset, logged and kept in `metrics[name]['bias']`, not part of the error.
+The two flags exclude each other.
 """
 import os
 import time
@@ -36,6 +43,7 @@ import torch
 import yaml
 
 from . import archs as _archs
+from . import camnoise as CN
 from . import data as _data
 from . import distributed as D
 from . import pgnoise as PG
@@ -84,6 +92,14 @@ class YOND_Full:
         self.device = torch.device('cuda', self.local_rank)
         torch.cuda.set_device(self.device)
         self.synth_noise = getattr(self.parser, 'synth_noise', None)    # (K, sigma) in DN, or None
+        self.camera_noise = getattr(self.parser, 'camera_noise', None)  # the --camera-noise spec (camnoise.camera_noise_arg), or None
+        if self.synth_noise is not None and self.camera_noise is not None:
+            raise SystemExit("--synth-noise and --camera-noise exclude each other: one noise model makes the frames (--camera-noise code=p,K=..,sigGs=.. "
+                             "is --synth-noise K,SIGMA)")
+        # the Poisson-Gaussian level in DN at capture that the estimator is measured against, whichever flag makes the noise
+        self.true_level = self.synth_noise
+        if self.camera_noise is not None:
+            self.true_level = CN.effective_pg(self.camera_noise, self.camera_noise['code'], self.camera_noise['mfm'])
         self.arch, self.pipe = self.args['arch'], dict(self.args['pipeline'])
         if self.pipe.get('bias_corr') == 'none':
             self.pipe['bias_corr'] = None
@@ -122,19 +138,24 @@ class YOND_Full:
                 self.dst_eval = ds
         if self.dst_eval is None or (len(self.dst_eval) == 0 and cls == 'Any_Dataset'):
             self.dst_eval = SyntheticFrames(self.parser.synthetic, int(self.dst.get('H', 3472)), int(self.dst.get('W', 4624)),
-                                            clean_only=self.synth_noise is not None)
+                                            clean_only=self.true_level is not None)
 
     def synthesise(self, data, wp, bl):
-        """--synth-noise: the item's clean frame becomes its ground truth and a noisy frame made from it on the current stream its
-        input (one yond_pg_noise_f32 launch; the same name gives the same noise)."""
-        K, sigma = self.synth_noise
+        """--synth-noise / --camera-noise: the item's clean frame becomes its ground truth and a noisy frame made from it on the current
+        stream its input (one yond_pg_noise_f32 or yond_camera_noise_f32 launch; the same name gives the same noise)."""
         clean = data['hr'] if data.get('hr') is not None else data['lr']
         if not isinstance(clean, torch.Tensor):
             clean = torch.from_numpy(np.ascontiguousarray(clean, np.float32))
         clean = clean.to(self.device, torch.float32).contiguous()
         data['hr'] = clean
-        data['lr'] = PG.add_pg_noise(clean, K, sigma, wp - bl, zlib.crc32(str(data['name']).encode()), [0],
-                                     exposure=1.0 / float(data.get('ratio', 1)))
+        key = zlib.crc32(str(data['name']).encode())
+        if self.camera_noise is not None:
+            spec = self.camera_noise
+            data['lr'] = CN.add_camera_noise(clean, dict(spec, wp=wp, bl=bl), spec['code'], wp - bl, key, [0], layout=CN.LAYOUT_BAYER,
+                                             ratio=float(data.get('ratio', 1)), mfm=spec['mfm'], clip=spec['clip'])
+            return data
+        K, sigma = self.synth_noise
+        data['lr'] = PG.add_pg_noise(clean, K, sigma, wp - bl, key, [0], exposure=1.0 / float(data.get('ratio', 1)))
         return data
 
     def IterDenoise(self, data, params):
@@ -205,11 +226,11 @@ class YOND_Full:
                     sums.update(psnrs, ssims)
                 self.metrics[data['name']] = {'psnr': psnrs, 'ssim': ssims, 'reg': res['regs']}
                 true = ""
-                if self.synth_noise is not None:
+                if self.true_level is not None:
                     # the pipeline's (K, sigma) are DN of the frame it is handed (YOND_SIDD.py:356 scales by wp - bl), digital gain
                     # included: a frame exposed at 1 / ratio and scaled back by ratio carries ratio * K and ratio * SIGMA
                     ratio = float(data.get('ratio', 1))
-                    K, sigma = self.synth_noise[0] * ratio, self.synth_noise[1] * ratio
+                    K, sigma = self.true_level[0] * ratio, self.true_level[1] * ratio
                     # (SIGMA = 0, pure shot noise, has no relative error: None there, and no share in the sweep's mean)
                     rel = [(float(abs(q[0] - K) / K), float(abs(q[1] - sigma) / sigma) if sigma > 0 else None) for q in res['params']]
                     self.metrics[data['name']].update(true=(K, sigma), rel_err=rel)
@@ -220,6 +241,10 @@ class YOND_Full:
                             rel_sums[4 * it + 2] += rs
                             rel_sums[4 * it + 3] += 1
                     true = f", true K={K:.3f}, sigma={sigma:.3f}"
+                    if self.camera_noise is not None and 'd' in self.camera_noise['code']:
+                        bias = [float(v) * ratio for v in CN.dark_bias(self.camera_noise, self.camera_noise['code'])]
+                        self.metrics[data['name']]['bias'] = bias
+                        true += ", dark bias " + "/".join(f"{v:.3f}" for v in bias)
                 log(f"[rank {self.rank}] {data['name']}: " + (f"PSNR={psnrs[-1]:.2f}, SSIM={ssims[-1]:.4f}" if psnrs else "denoised (no reference frame)")
                     + f", K={res['params'][-1][0]:.3f}, sigma={res['params'][-1][1]:.3f}" + true, self.logfile)
 
@@ -239,7 +264,7 @@ class YOND_Full:
 
                 def feed():
                     for k, data in loader:
-                        if self.synth_noise is not None:
+                        if self.true_level is not None:
                             data = self.synthesise(data, wp, bl)
                         queue.append((k, data))
                         yield data['lr'], params_of(data)
@@ -252,7 +277,7 @@ class YOND_Full:
                 t_path += time.perf_counter() - t1           # (includes what the loop waited for its loader threads)
             else:
                 for k, data in loader:
-                    if self.synth_noise is not None:
+                    if self.true_level is not None:
                         data = self.synthesise(data, wp, bl)
                     torch.cuda.synchronize()
                     t1 = time.perf_counter()
@@ -264,7 +289,7 @@ class YOND_Full:
             torch.cuda.synchronize()
             dt = D.max_over_ranks(time.perf_counter() - t0, self.device)
             red = sums.reduce(self.device)
-            if self.synth_noise is not None:
+            if self.true_level is not None:
                 rel = D.sum_over_ranks(rel_sums, self.device)
                 for it in range(n_it):
                     if rel[4 * it + 1]:

@@ -95,6 +95,7 @@ PROTOTYPES = {
     "yond_clock_probe": [f64, vp, vp],
     "yond_img2raw_f32": [vp, sz, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp],
     "yond_pg_noise_f32": [vp, vp, sz, i32, vp, i32, vp],
+    "yond_camera_noise_f32": [vp, vp, sz, i32, vp, i32, i32, vp],
     "yond_est_conv_in_f32": [vp, i32, i32, i32, i32, vp, vp, vp, vp],
     "yond_est_head_f32": [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp],
     "yond_est_head_ws_bytes": [i32, i32],
