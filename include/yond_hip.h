@@ -116,7 +116,9 @@ int yond_nchw4_to_nhwc4_f32(const float* src, float* dst, int N, int H, int W, v
 int yond_nhwc4_to_nchw4_f32(const float* src, float* dst, int N, int H, int W, void* stream);
 
 /* Per-image maximum (archs/modules.py:18-19).  x: [N][elems]; partial: workspace float[N*256];
- * out: float[N].  Two launches, deterministic. */
+ * out: float[N].  Two launches, deterministic.  A NaN is DROPPED, not propagated (every step is fmaxf, which returns its other
+ * operand): out[n] is the maximum of the image's non-NaN elements, -inf for an image that is all NaN -- where torch's x.max() returns
+ * NaN.  A caller that needs to notice a NaN has to look for it itself; -inf and +inf are ordinary values here. */
 int yond_image_max_f32(const float* x, int N, size_t elems, float* partial, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
@@ -751,7 +753,8 @@ int yond_camera_noise_f32(const float* clean, float* noisy, size_t n_per_item, i
  *   yond_est_conv_in_f32  3x3 on ONE full-resolution plane x [N][H][W], zero padding 1, + bias, ReLU -> dst [N][H][W][Cout].
  *                         w [Cout][9] and bias [Cout] on the device, zero-padded to Cout (a multiple of 32, <= 1024).
  *                         64-bit element offsets.  HBM bound: 4 B in, 4 Cout B out per pixel.
- *   yond_est_head_f32     1x1 from feat [N][H][W][Cin] (Cin a multiple of 4) to out_nc <= 4 channels (w [out_nc][Cin], bias [out_nc]),
+ *   yond_est_head_f32     1x1 from feat [N][H][W][Cin] (Cin a multiple of 4, <= 4096, and out_nc * Cin * 4 + 512 bytes of LDS at most
+ *                         64 KiB: Cin = 4096 with out_nc = 4 is YOND_EUNSUPPORTED) to out_nc <= 4 channels (w [out_nc][Cin], bias [out_nc]),
  *                         squared when sq != 0 ('var').  pge 0: out is the map [N][out_nc][H][W].  pge 1: out is the spatial mean
  *                         [N][out_nc]; partial (device, yond_est_head_ws_bytes(N, out_nc) bytes = N * YOND_EST_HEAD_BLOCKS * out_nc
  *                         doubles) holds per-workgroup float64 sums, added in a fixed order by a second launch: the same input gives

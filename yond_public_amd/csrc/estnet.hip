@@ -155,6 +155,9 @@ extern "C" int yond_est_head_f32(const float* feat, int N, int H, int W, int Cin
                                  int sq, int pge, float* out, double* partial, void* stream) {
     if (!feat || !w || !bias || !out || N <= 0 || H <= 0 || W <= 0 || N > 65535) return YOND_EINVAL;
     if (out_nc < 1 || out_nc > 4 || Cin <= 0 || Cin % 4 != 0 || Cin > 4096) return YOND_EUNSUPPORTED;
+    // the weights [out_nc][Cin] (dynamic LDS) sit beside s_red (static, EST_PPI x 4 doubles): together they must fit the 64 KiB a
+    // workgroup gets without hipFuncSetAttribute, or the launch fails.  Cin = 4096 with out_nc = 4 is 64 KiB + 512 B: refused.
+    if ((size_t)out_nc * Cin * sizeof(float) + EST_PPI * 4 * sizeof(double) > 65536) return YOND_EUNSUPPORTED;
     if (pge && !partial) return YOND_EINVAL;
     const long long HW = (long long)H * W;
     const long long groups = (HW + EST_PPI - 1) / EST_PPI;

@@ -33,6 +33,9 @@ def _np_ptr(a):
     return C.c_void_p(a.ctypes.data)
 
 
+FILM_MAX_C = 1024                   # widest block of yond_film_f32 (YondFilmDesc.C, include/yond_hip.h)
+
+
 # 3x3 stride-1 layers: 1 = Winograd F(2x2,3x3) wherever the kernel supports the shape (measured 1.45-1.5x over the direct
 # kernel at 64..512 channels, 1.15x on the 32-channel level-0 layers), 0 = direct implicit GEMM everywhere
 WINO_DEFAULT = 'split'              # 'split': fp32-accurate split-operand fp16-MFMA kernels where they apply, fp32 Winograd elsewhere;
@@ -532,6 +535,11 @@ class DenoiserPlan:
 
     def _film(self, t_dev, ub, N):
         """All nine blocks' (scale, shift) epilogue vectors in one launch."""
+        wide = [(pre, c) for pre, c in self._film_spec if c > FILM_MAX_C]
+        if wide:
+            # film_kernel stages a block's C-vector in s_h[FILM_MAX_C] (csrc/conv_misc.hip): a wider block would write past it
+            raise ValueError(f"yond_film_f32 covers blocks of at most {FILM_MAX_C} channels; "
+                             f"{wide[0][0]} has {wide[0][1]} (a guided net with nf = 128 reaches 2048 at its deepest level)")
         key = (N, getattr(self, 'lane', 0))
         if key not in self._film_cache:
             fp = self._film_params
