@@ -784,6 +784,43 @@ int yond_raw_ingest_f32(const float* raw, size_t n, float bl, float ratio, float
 int yond_raw_emit_u16(const float* x, size_t n, float bl, float scale, float ratio, int undo_gain, uint16_t* out,
                       unsigned long long* n_saturated, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * K7r  the robust noise-level fit: utils/isp_algos.py:345-362 with ransac=True (ransac.hip) -- sklearn's RANSACRegressor around a
+ * LinearRegression with min_samples = int(sqrt(n)), which the reference ships unused for its host cost (YOND_SIDD.py:85, 113).
+ * Every sum is accumulated in a fixed order (no float64 atomics): the same input gives the same bits.
+ *   yond_ransac_compact_f32  the pairs (x = mean, y = var) of the elements with lap < *th (th: one float64 on the device; lap may be
+ *       null: every element), in the order of NumPy's var[img_lap < th] on the reference's [h][w][nch] arrays: the maps here are
+ *       planar [nch][npix] (nch 1..4; flat arrays: nch = 1), the output ascends in pixel * nch + c.  tile_w > 0 (rows of 32 tile_w
+ *       pixels): the SIDD_256 re-tiling of YOND_SIDD.py:65, 92-93, whose array is [h][tile_w][32 * nch] -- the output ascends in
+ *       ((row * tile_w + j) * 32 + tile) * nch + c for the pixel at column tile * tile_w + j.  polyfit's non-saturation rule
+ *       (:348-350) is applied: only 1e-4 < x < 0.8 when that keeps more than 1 % of the selected points, else all of them.
+ *       x, y: room for nch * npix floats each.  result (device, 3 int64): {n kept, n selected before the rule, rule applied}.
+ *       ws: yond_ransac_compact_ws_bytes(npix) bytes, 8-byte aligned.  Per-workgroup counts (tiles of YOND_RANSAC_TILE pixels),
+ *       one scan, one scatter.
+ *   yond_ransac_absdev_f32   d[i] = |y[i] - med| in float32, med = (med2[0] + med2[1]) / 2 in float32: np.median's value from the two
+ *       middle order statistics (ranks (n - 1) / 2 and n / 2 of yond_select_ranks_f32; device).  sklearn's default
+ *       residual_threshold is the median of d.
+ *   yond_ransac_trials_f32   idx: int32 [T][m] sample indices into (x, y) (device; T <= YOND_RANSAC_MAXT, 1 <= m <= n); thr2: the two
+ *       middle order statistics of d (device).  out (device, [T][YOND_RANSAC_COLS] float64), per trial:
+ *         [0] slope, [1] intercept of the centred least-squares line through the trial's samples (float64);
+ *         [2] count, [3] Sx, [4] Sy, [5] Sxx, [6] Sxy, [7] Syy, [8] Srr over the inliers, r = |y - (slope x + intercept)| <= thr
+ *             in float64 (what sklearn's R^2 and the refit of the winner need);
+ *         [9] thr (the float32 threshold, the same in every row).
+ *       ws: yond_ransac_ws_bytes(n, T) bytes (per-workgroup partial sums, chunks of YOND_RANSAC_CHUNK points), 8-byte aligned.
+ * Refused (YOND_EINVAL, nothing launched): a null pointer other than lap, npix == 0, nch outside 1..4, n < 2, T or m out of range,
+ * a misaligned workspace. */
+#define YOND_RANSAC_TILE 1024
+#define YOND_RANSAC_CHUNK 2048
+#define YOND_RANSAC_MAXT 128
+#define YOND_RANSAC_COLS 10
+size_t yond_ransac_compact_ws_bytes(size_t npix);
+int yond_ransac_compact_f32(const float* lap, const float* mean, const float* var, size_t npix, int nch, int tile_w,
+                            const double* th, float* x, float* y, long long* result, void* ws, void* stream);
+int yond_ransac_absdev_f32(const float* y, size_t n, const float* med2, float* d, void* stream);
+size_t yond_ransac_ws_bytes(size_t n, int T);
+int yond_ransac_trials_f32(const float* x, const float* y, size_t n, const int32_t* idx, int T, int m, const float* thr2,
+                           double* out, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -146,6 +146,9 @@ class YOND_SIDD:
         self.dst, self.arch, self.pipe = self.args['dst'], self.args['arch'], self.args['pipeline']
         if self.pipe['bias_corr'] == 'none':
             self.pipe['bias_corr'] = None
+        if getattr(self.parser, 'fit', None) is not None:                            # --fit overrides the runfile's pipeline.est_fit
+            self.pipe['est_fit'] = self.parser.fit
+        P.est_fit_of(self.pipe)                                                      # ('ransac': no device chain, images one at a time)
         self.model_name, self.method_name = self.args['model_name'], self.args['method_name']
         self.fast_ckpt = self.args['fast_ckpt']
         self.save_plot = bool(getattr(self.parser, 'fig', False))                    # YOND_SIDD.py:153
@@ -519,6 +522,9 @@ class YONDParser:
                        "writes the reference's cache npy/<method_name>/<k:03d>.npy, float32 [max_iter + 1][256][8192]")
         a.add_argument('--host-ingest', dest='host_ingest', action='store_true', default=False, help="full-frame drivers: normalise the raw frames on the host in "
                        "NumPy and upload float32 (the earlier path) instead of uploading the raw DN and normalising on the device")
+        a.add_argument('--fit', choices=('lsq', 'ransac'), default=None, help="the line fit of the noise-level estimate: lsq, the reference's shipped least "
+                       "squares (default), or ransac, its polyfit(ransac=True) replayed on the GPU (needs scikit-learn for the subset draws; frames are then "
+                       "estimated one at a time, outside the device chain).  Overrides the runfile's pipeline.est_fit")
         from .pgnoise import synth_noise_arg
         a.add_argument('--synth-noise', dest='synth_noise', type=synth_noise_arg, default=None, metavar='K,SIGMA', help="full-frame drivers: take every item's clean "
                        "frame (hr if present, else lr) as the ground truth and make the noisy frame on the GPU, Poisson-Gaussian with system gain K and read "

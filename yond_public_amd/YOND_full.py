@@ -104,6 +104,9 @@ class YOND_Full:
         if self.pipe.get('bias_corr') == 'none':
             self.pipe['bias_corr'] = None
         self.pipe.setdefault('k', 29)                                   # (the ANY runfile leaves k to the driver's default)
+        if getattr(self.parser, 'fit', None) is not None:               # --fit overrides the runfile's pipeline.est_fit
+            self.pipe['est_fit'] = self.parser.fit
+        self.fit = P.est_fit_of(self.pipe)                              # 'ransac': frames take IterDenoise one at a time (stream_applies)
         if not self.pipe.get('full_dn', False):
             raise SystemExit(f"{self.parser.runfile}: the full-frame drivers run runfiles with `full_dn: True` (YOND_SIDD.py handles the block layout)")
         self.model_name, self.method_name = self.args['model_name'], self.args['method_name']
@@ -302,7 +305,7 @@ class YOND_Full:
                 if red['count']:
                     for it in range(n_it):
                         log(f"Iter{it}: PSNR={red[f'psnr_iter{it}']:.2f}, SSIM={red[f'ssim_iter{it}']:.4f}"
-                            + (f", mean |K_est - K| / K = {red[f'rel_err_K_iter{it}']:.4f}" if f'rel_err_K_iter{it}' in red else "")
+                            + (f", fit {self.fit}: mean |K_est - K| / K = {red[f'rel_err_K_iter{it}']:.4f}" if f'rel_err_K_iter{it}' in red else "")
                             + (f", mean |sigma_est - sigma| / sigma = {red[f'rel_err_sigma_iter{it}']:.4f}" if f'rel_err_sigma_iter{it}' in red else ""),
                             self.logfile)
                     log(f"Iter_last: PSNR={red['psnr_last']:.2f}, SSIM={red['ssim_last']:.4f}", self.logfile)

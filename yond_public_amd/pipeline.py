@@ -380,6 +380,157 @@ def _fit_from_moments(m_all, m_ns):
     return np.array([(n * sxy - sx * sy) / det, (sxx * sy - sx * sxy) / det])
 
 
+# ---- the robust fit: utils/isp_algos.py:353-362, sklearn's RANSACRegressor(min_samples=int(sqrt(n))) around a LinearRegression ----
+RANSAC_TRIALS = 100                 # RANSACRegressor's max_trials
+RANSAC_SEED = 2024                  # polyfit's setup_seed(2024) (:346): random_state=None draws from the global NumPy state it seeded
+FITS = ('lsq', 'ransac')
+
+
+def est_fit_of(pipe):
+    """pipe['est_fit'] (the drivers' --fit / the runfile's pipeline.est_fit): 'lsq' (default, the reference's shipped fit) or 'ransac'."""
+    fit = (pipe or {}).get('est_fit', 'lsq')
+    if fit not in FITS:
+        raise L.YondHipError(f"est_fit {fit!r}: one of {FITS}")
+    return fit
+
+
+_NOTED = set()
+
+
+def _ransac_stream_note(who, log=None):
+    """est_fit 'ransac' takes the stream drivers' one-frame-at-a-time fallback: said once per driver."""
+    if who in _NOTED:
+        return
+    _NOTED.add(who)
+    msg = f"{who}: est_fit 'ransac' is outside the device chain -- falling back to IterDenoise, one frame at a time"
+    if log:
+        log(msg)
+    else:
+        import sys
+        print(msg, file=sys.stderr, flush=True)
+
+
+def ransac_subsets(n, m, trials=RANSAC_TRIALS, seed=RANSAC_SEED):
+    """int32 [trials][m]: the sample sets RANSACRegressor.fit draws for n points (one sample_without_replacement per trial from
+    one RandomState; sklearn draws them lazily inside its loop, in the same order, and nothing else consumes the stream)."""
+    return _ransac_drawer(n, m, seed)(trials)
+
+
+RANSAC_BATCHES = (2, 4, 8, 16, 32, 38)      # trials per launch of the scoring pass: RANSAC_TRIALS in all
+
+
+def _ransac_drawer(n, m, seed=RANSAC_SEED):
+    """draw(count) -> int32 [count][m]: the next `count` subsets of ransac_subsets(n, m)'s stream."""
+    try:
+        from sklearn.utils.random import sample_without_replacement
+    except ImportError as e:
+        raise L.YondHipError("the RANSAC fit draws its subsets with sklearn.utils.random.sample_without_replacement, as the reference's "
+                             "RANSACRegressor does: scikit-learn is not installed") from e
+    rs = np.random.RandomState(seed)
+    return lambda count: np.stack([sample_without_replacement(n, m, random_state=rs) for _ in range(count)]).astype(np.int32)
+
+
+def _ransac_dynamic_max_trials(n_inliers, n, m, probability=0.99):
+    """sklearn.linear_model._ransac._dynamic_max_trials with the same NumPy calls."""
+    eps = np.spacing(1)
+    ratio = np.float64(n_inliers) / float(n)
+    nom = max(eps, 1 - probability)
+    denom = max(eps, 1 - ratio ** m)
+    if denom == 1:
+        return float('inf')
+    return abs(float(np.ceil(np.log(nom) / np.log(denom))))
+
+
+def _ransac_select(tab, n, m, total=None):
+    """RANSACRegressor.fit's loop over the trial table [T][>= 9] = {slope, intercept, count, Sx, Sy, Sxx, Sxy, Syy, Srr}:
+    a trial with fewer inliers than the best is skipped, one with as many and a lower R^2 too; every new best shrinks max_trials.
+    Returns (winning trial, its inlier count, trials run).  `total`: max_trials when `tab` holds only the first rows of the table;
+    None is returned when the loop needs a row that is not there yet."""
+    best, n_best, score_best = -1, 1, -np.inf
+    max_trials, trials = (len(tab) if total is None else total), 0
+    while trials < max_trials:
+        if trials >= len(tab):
+            return None                              # the loop goes on past the rows computed so far
+        t = trials
+        trials += 1
+        cnt = int(tab[t][2])
+        if cnt < n_best:
+            continue
+        sy, syy, srr = float(tab[t][4]), float(tab[t][7]), float(tab[t][8])
+        den = syy - sy * sy / cnt if cnt > 0 else 0.0
+        if cnt < 2 or den <= 0:                      # r2_score(force_finite=True): constant y
+            score = 1.0 if srr == 0 else 0.0
+        else:
+            score = 1.0 - srr / den
+        if cnt == n_best and score < score_best:
+            continue
+        best, n_best, score_best = t, cnt, score
+        max_trials = min(max_trials, _ransac_dynamic_max_trials(n_best, n, m))
+    if best < 0:
+        raise L.YondHipError("RANSAC could not find a valid consensus set: no trial has an inlier")   # (sklearn: ValueError)
+    return best, n_best, trials
+
+
+def _ransac_median2(data, n, lib, st):
+    """The two middle order statistics of data[:n] (device float32 [2]): np.median is their float32 mean."""
+    ranks = np.array([(n - 1) // 2, n // 2], dtype=np.int64)
+    ws = torch.empty(int(lib.yond_select_ws_bytes(2)), dtype=torch.uint8, device=data.device)
+    out = torch.empty(2, dtype=torch.float32, device=data.device)
+    L.check(lib.yond_select_ranks_f32(L.ptr(data), n, C.c_void_p(ranks.ctypes.data), 2, L.ptr(out), L.ptr(ws), st), "yond_select_ranks_f32")
+    return out
+
+
+def _ransac_fit(lap, mean, var, th_dev, nch, tile_w=0, full=False):
+    """polyfit(mean[lap < th], var[lap < th], ransac=True) of planar device maps [nch][npix] (flat, contiguous float32; lap None:
+    every element): compaction in the reference's order with the non-saturation rule -> n (one host sync) -> MAD threshold by two
+    exact selections -> per batch of trials: subsets drawn on the host, trial fits and the scoring pass, the rows of the [T][10] table
+    back (one sync per batch, one to six batches), sklearn's selection loop on the rows so far -> the refit of the winner from its
+    inliers' moment sums, on the host.  info['table'] holds the rows computed, at least n_trials of them."""
+    lib = L.load()
+    st = L.stream()
+    dev = mean.device
+    npix = mean.numel() // nch
+    x = torch.empty(nch * npix, dtype=torch.float32, device=dev)
+    y = torch.empty(nch * npix, dtype=torch.float32, device=dev)
+    res = torch.empty(3, dtype=torch.int64, device=dev)
+    cws = torch.empty(int(lib.yond_ransac_compact_ws_bytes(npix)), dtype=torch.uint8, device=dev)
+    with _stage("nle_ransac"):
+        L.check(lib.yond_ransac_compact_f32(L.ptr(lap), L.ptr(mean), L.ptr(var), npix, nch, int(tile_w), L.ptr(th_dev), L.ptr(x), L.ptr(y),
+                                            L.ptr(res), L.ptr(cws), st), "yond_ransac_compact_f32")
+        n, n_sel, masked = (int(v) for v in res.cpu().numpy())            # the fit's one extra sync before its result
+        if n < 2:
+            raise L.YondHipError(f"polyfit(ransac=True) needs at least 2 points, got {n}")
+        m = int(np.sqrt(n))                                                # :354 min_samples
+        med2 = _ransac_median2(y, n, lib, st)
+        d = torch.empty(n, dtype=torch.float32, device=dev)
+        L.check(lib.yond_ransac_absdev_f32(L.ptr(y), n, L.ptr(med2), L.ptr(d), st), "yond_ransac_absdev_f32")
+        thr2 = _ransac_median2(d, n, lib, st)
+        # sklearn draws a subset per trial INSIDE its loop and stops when the dynamic rule says so (on a clean frame after two
+        # trials), and a draw of m from millions costs the host milliseconds: the trials run in growing batches -- the stream of one
+        # RandomState is the same however it is cut -- and the loop is replayed on the rows so far after each (one sync per batch)
+        draw = _ransac_drawer(n, m)
+        T = RANSAC_TRIALS
+        tab = torch.empty((T, 10), dtype=torch.float64, device=dev)
+        ws = torch.empty(int(lib.yond_ransac_ws_bytes(n, max(RANSAC_BATCHES))), dtype=torch.uint8, device=dev)
+        done, picked = 0, None
+        for b in RANSAC_BATCHES:
+            idx_dev = torch.from_numpy(draw(b)).to(dev)
+            L.check(lib.yond_ransac_trials_f32(L.ptr(x), L.ptr(y), n, L.ptr(idx_dev), b, m, L.ptr(thr2), L.ptr(tab[done:]), L.ptr(ws), st),
+                    "yond_ransac_trials_f32")
+            done += b
+            tab_h = tab[:done].cpu().numpy()
+            picked = _ransac_select(tab_h, n, m, total=T)
+            if picked is not None:
+                break
+    win, n_in, n_trials = picked
+    mom = tab_h[win, 2:7]                                                  # {n, Sx, Sy, Sxx, Sxy} over the winner's inliers
+    reg = _fit_from_moments(mom, mom)
+    if full:
+        return reg, dict(n=n, n_selected=n_sel, nonsat=bool(masked), m=m, thr=np.float32(tab_h[0, 9]), winner=win, n_inliers=n_in,
+                         n_trials=n_trials, table=tab_h)
+    return reg
+
+
 def _same(a, b):
     """Equality of two float64 results of the same formula, NaN included (a frame with NaN pixels has NaN percentiles on both
     sides: the reference carries them through; the cross-check must not turn that into an error)."""
@@ -451,10 +602,12 @@ def _nle_workspace(n, dev):
     return torch.empty(int(L.load().yond_nle_ws_bytes(n)), dtype=torch.uint8, device=dev)
 
 
-def _nlf_from_maps(lap, mean, var, full=False, ws=None):
+def _nlf_from_maps(lap, mean, var, full=False, ws=None, fit='lsq', tile_w=0):
     """Shared tail of SelfNLF / CollabNLF (YOND_SIDD.py:75-87 / 103-115).  Percentiles, occupancy, score3 and the
     moment sums below the selected threshold all run on the device; one host sync at the end.  `ws`: the workspace the
-    producer of the maps has already filled with the level-1 statistics (fused box kernel), else a sweep does it."""
+    producer of the maps has already filled with the level-1 statistics (fused box kernel), else a sweep does it.
+    fit 'ransac': the line comes from polyfit(..., ransac=True) on the points below the same threshold (the maps are then the
+    planar [4][h][w] of SimpleNLF; tile_w: its SIDD_256 re-tiling, which decides the order of the points)."""
     lib = L.load()
     width = lap.shape[-1] if lap.dim() > 1 else lap.numel()
     lap, mean, var = lap.reshape(-1), mean.reshape(-1), var.reshape(-1)
@@ -482,17 +635,26 @@ def _nlf_from_maps(lap, mean, var, full=False, ws=None):
     if info['index'] != int(sel_h[0]) or not _same(th, sel_h[1]):   # host and device run the same float64 formula
         raise L.YondHipError(f"score3 mismatch: device picked {sel_h[0]:.0f}/{sel_h[1]!r}, host {info['index']}/{th!r}")
     sel = mom_h                                                  # pixels with lap < ths[i]
+    th_fit = th                                                  # the threshold whose selection is fitted
     if sel[0, 0] > 0:
         reg = _fit_from_moments(sel[0], sel[1])
     else:                                                        # :79-84 'no flat area'
         th_b = _percentiles(lap, [25.0])
         th_backup = float(th_b.cpu().numpy()[0])
         if th != th_backup:
-            th = th_backup
+            th = th_fit = th_backup
             sel = _moments(lap, mean, var, th_b).cpu().numpy()
         else:                                                    # same threshold: the empty selection falls back to all
+            th_fit = float('inf')
             sel = _moments(lap, mean, var, torch.full((1,), float('inf'), dtype=torch.float64, device=lap.device)).cpu().numpy()
         reg = _fit_from_moments(sel[0], sel[1])
+    if fit == 'ransac':                                          # :86 / :114 with ransac=True
+        th_dev = torch.full((1,), th_fit, dtype=torch.float64, device=lap.device)
+        reg, rinfo = _ransac_fit(lap, mean, var, th_dev, 4, tile_w=tile_w, full=True)
+        if full:
+            info['ransac'] = rinfo
+    elif fit != 'lsq':
+        raise L.YondHipError(f"fit {fit!r}: one of {FITS}")
     if full:
         info.update(th=th, percent=pct, nsel=int(sel[0, 0]))
         if frame_max_key:
@@ -517,7 +679,9 @@ def SimpleNLF(lr_raw, hr_raw=None, k=29, setting=None, full=False, device=None, 
       'plain'               the stand-alone kernels of the first version, followed by a separate statistics sweep (kept
                             for the function seam and as a cross-check).
     `fused` is the older spelling (True -> 'one-pass', False -> 'plain').  With full=True the info dict carries
-    'frame_max' (float32 maximum of lr_raw) except on the 'plain' path."""
+    'frame_max' (float32 maximum of lr_raw) except on the 'plain' path.
+    setting['fit'] = 'ransac' replaces the least-squares line of :86 / :114 by polyfit(..., ransac=True) on the same points
+    (info['ransac']: winner, counts, threshold and the trial table); 'lsq' is the default."""
     setting = setting or {'mode': 'self'}
     lib = L.load()
     lr = _dev(lr_raw, device)
@@ -576,7 +740,7 @@ def SimpleNLF(lr_raw, hr_raw=None, k=29, setting=None, full=False, device=None, 
         raise NotImplementedError(setting['mode'])
     if _maps_only:
         return lap, mean, var, ws
-    return _nlf_from_maps(lap, mean, var, full, ws=ws)
+    return _nlf_from_maps(lap, mean, var, full, ws=ws, fit=setting.get('fit', 'lsq'), tile_w=tile_w)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -776,7 +940,8 @@ def chain_applies(lr, net, arch, pipe, biaslut=None):
     """The configurations the device chain covers: one bare Bayer frame, full_dn, bias_corr 'pre' with the 1-D LUT."""
     return (isinstance(lr, torch.Tensor) and lr.is_cuda and lr.dim() == 2 and bool(pipe.get('full_dn', False)) and biaslut is None
             and pipe.get('bias_corr', 'pre') == 'pre' and pipe.get('full_est', True) and DEVICE_CHAIN
-            and 'simple' in str(pipe.get('est_type', 'simple')) and 'cal_est' not in pipe)
+            and 'simple' in str(pipe.get('est_type', 'simple')) and 'cal_est' not in pipe
+            and est_fit_of(pipe) == 'lsq')          # (the chain's fit is the least-squares one of yond_frame_params_f64)
 
 
 DEVICE_CHAIN = True                 # (module attribute: tools / tests switch the host-side chain back on for A/B)
@@ -958,6 +1123,7 @@ def chain_applies_sidd(lr, lr_full, net, arch, pipe, p, biaslut=None):
     return (isinstance(lr, torch.Tensor) and lr.is_cuda and lr.dim() == 3 and lr.shape[0] == 32 and not pipe.get('full_dn', False)
             and biaslut is None and pipe.get('bias_corr', 'pre') == 'pre' and pipe.get('full_est', True) and DEVICE_CHAIN and CHAIN_SIDD
             and 'simple' in str(pipe.get('est_type', 'simple')) and 'cal_est' not in pipe and 'rot_cfa' not in p
+            and est_fit_of(pipe) == 'lsq'
             and (lr_full is None or (isinstance(lr_full, torch.Tensor) and lr_full.is_cuda and lr_full.dim() == 2)))
 
 
@@ -1280,6 +1446,7 @@ def IterDenoise(lr_raw, net, arch, pipe, lr_full=None, p=None, device=None, log=
     check_estimate_config(pipe, est)
     p = dict(p or default_params())
     k = pipe.get('k', 29)
+    fit = est_fit_of(pipe)                     # 'ransac': the device chain does not apply, both rounds estimate frame by frame here
     bias_corr = pipe.get('bias_corr', 'pre')
     if bias_corr == 'none':
         bias_corr = None
@@ -1344,10 +1511,10 @@ def IterDenoise(lr_raw, net, arch, pipe, lr_full=None, p=None, device=None, log=
     elif 'ours' in est_type:                                                           # :342-348: NeuralNLF = SimpleNLF with est_self's k
         k = _section_k(est, 'est_self')                                                # (the network it is handed is never read)
         lr_max_dev = _frame_max(lr_cat) if lr_full is not None else None
-        reg, nle_info = SimpleNLF(raw4est, k=k, setting={'mode': 'self'}, full=True)
+        reg, nle_info = SimpleNLF(raw4est, k=k, setting={'mode': 'self', 'fit': fit}, full=True)
     elif 'simple' in est_type:
         lr_max_dev = _frame_max(lr_cat) if lr_full is not None else None
-        reg, nle_info = SimpleNLF(raw4est, k=k, setting={'mode': 'self'}, full=True)   # :341
+        reg, nle_info = SimpleNLF(raw4est, k=k, setting={'mode': 'self', 'fit': fit}, full=True)   # :341
     elif 'manual' in est_type:                                                         # :349-351: a fixed (K, sigma) = (14, 20) DN
         reg = (14 / (p['wp'] - p['bl']), (20 / (p['wp'] - p['bl'])) ** 2)
         lr_max_dev, nle_info = _frame_max(lr_cat), {}
@@ -1396,8 +1563,8 @@ def IterDenoise(lr_raw, net, arch, pipe, lr_full=None, p=None, device=None, log=
             can_tile = (lr_cat.shape[-1] // 2) % 32 == 0
             if 'ours' in est_type:                                                     # :425-429: NeuralNLF = SimpleNLF with est_collab's k
                 k = _section_k(est, 'est_collab')
-            reg = SimpleNLF(lr_cat, raw_dn, k=k,
-                            setting={'mode': 'collab', 'SIDD_256': bool(pipe.get('collab_sidd256', sidd or stack or can_tile))})   # :431
+            reg = SimpleNLF(lr_cat, raw_dn, k=k, setting={'mode': 'collab', 'fit': fit,
+                                                          'SIDD_256': bool(pipe.get('collab_sidd256', sidd or stack or can_tile))})   # :431
             if reg[1] < 0:                                                             # :438-440
                 reg = (reg[0], reg[0] ** 2)
             p['gain'], p['sigma'] = reg[0] * scale, np.sqrt(reg[1]) * scale            # :442
@@ -1449,6 +1616,8 @@ def denoise_stream_groups(groups, net, arch, pipe, p=None, device=None, log=None
     flag the chain leaves to the host, go through IterDenoiseGroup / IterDenoise when they are yielded.  Items must stay unmodified until yielded."""
     p0 = dict(p or default_params())
     two = pipe.get('iter', 'iter') == 'iter' and pipe.get('max_iter', 1) == 1
+    if est_fit_of(pipe) != 'lsq':              # (usable() is then false for every group: IterDenoise image by image)
+        _ransac_stream_note('denoise_stream_groups', log)
     main = torch.cuda.current_stream()
     side = _side_stream(main.device)
     RING = 4
@@ -1604,6 +1773,9 @@ def denoise_stream_batches(frames, B, net, arch, pipe, p=None, device=None):
 
     chain_cfg = (DEVICE_CHAIN and STREAM_GROUPS and pipe.get('iter', 'iter') == 'once' and pipe.get('full_dn', False) and pipe.get('bias_corr', 'pre') == 'pre'
                  and 'simple' in str(pipe.get('est_type', 'simple')) and 'cal_est' not in pipe and pipe.get('full_est', True) and 'rot_cfa' not in p0)
+    if est_fit_of(pipe) != 'lsq':
+        _ransac_stream_note('denoise_stream_batches')
+        chain_cfg = False
     if not chain_cfg:
         while True:
             batch = take()
@@ -1700,7 +1872,8 @@ def IterDenoiseBatch(frames, net, arch, pipe, p=None, device=None):
     lrs = [_dev(f, device) for f in frames]
     B = len(lrs)
     stack = torch.stack(lrs)
-    est = [SimpleNLF(f, k=k, setting={'mode': 'self'}, full=True) for f in lrs]          # :341 per frame
+    fit = est_fit_of(pipe)
+    est = [SimpleNLF(f, k=k, setting={'mode': 'self', 'fit': fit}, full=True) for f in lrs]   # :341 per frame
     regs = [e[0] for e in est]
     maxes = [np.float32(e[1]['frame_max']) if 'frame_max' in e[1] else np.float32(_frame_max(f).item()) for e, f in zip(est, lrs)]
     ps = [dict(p0, gain=r[0] * scale, sigma=np.sqrt(max(r[1], 0)) * scale) for r in regs]  # :356
@@ -1712,7 +1885,8 @@ def IterDenoiseBatch(frames, net, arch, pipe, p=None, device=None):
             regs2, ps2, funcs = [], [], []
             for i in range(B):
                 can_tile = (lrs[i].shape[-1] // 2) % 32 == 0                                # as IterDenoise: where the reference's split runs
-                reg = SimpleNLF(lrs[i], raw_dn[i], k=k, setting={'mode': 'collab', 'SIDD_256': bool(pipe.get('collab_sidd256', can_tile))})
+                reg = SimpleNLF(lrs[i], raw_dn[i], k=k, setting={'mode': 'collab', 'fit': fit,
+                                                                 'SIDD_256': bool(pipe.get('collab_sidd256', can_tile))})
                 if reg[1] < 0:                                                             # :438-440
                     reg = (reg[0], reg[0] ** 2)
                 if reg[0] < 0:                                                             # :445-447: this frame keeps its round-1 result
@@ -1742,7 +1916,8 @@ def stream_applies(pipe, p=None, biaslut=None):
     """True when denoise_stream runs one of its device-chain drivers for this configuration (full-frame denoising, bias_corr 'pre' with the 1-D LUT,
     est_type 'simple', 'once' or the shipped 'iter' with max_iter 1) -- the configurations in which `frames` may carry per-frame parameter dicts."""
     ok = (DEVICE_CHAIN and bool(pipe.get('full_dn', False)) and pipe.get('bias_corr', 'pre') == 'pre' and 'simple' in str(pipe.get('est_type', 'simple'))
-          and 'cal_est' not in pipe and pipe.get('full_est', True) and 'rot_cfa' not in (p or {}) and biaslut is None)
+          and 'cal_est' not in pipe and pipe.get('full_est', True) and 'rot_cfa' not in (p or {}) and biaslut is None
+          and est_fit_of(pipe) == 'lsq')
     mode = pipe.get('iter', 'iter')
     return ok and (mode == 'once' or (mode == 'iter' and pipe.get('max_iter', 1) == 1 and STREAM_ITER))
 
@@ -1759,6 +1934,12 @@ def denoise_stream(frames, net, arch, pipe, p=None, device=None):
     been yielded -- a producer that refills one buffer in place must hand in clones.
     An element of `frames` may be a pair (frame, p): a frame with its own parameter dict (wp / bl / ratio / scale: the evaluation drivers' items) --
     in the configurations `stream_applies` names."""
+    if est_fit_of(pipe) != 'lsq':
+        _ransac_stream_note('denoise_stream')
+        for f in frames:
+            f, pk = f if isinstance(f, tuple) else (f, p)
+            yield IterDenoise(f, net, arch, pipe, p=pk, device=device)
+        return
     chain_cfg = (DEVICE_CHAIN and pipe.get('bias_corr', 'pre') == 'pre' and 'simple' in str(pipe.get('est_type', 'simple')) and 'cal_est' not in pipe
                  and pipe.get('full_est', True) and 'rot_cfa' not in (p or {}))
     if pipe.get('full_dn', False) and pipe.get('iter', 'iter') == 'iter' and pipe.get('max_iter', 1) == 1 and chain_cfg and STREAM_ITER:

@@ -88,12 +88,18 @@ def varfilt(img, k=5):
     return s * s
 
 
-def polyfit(x, y, ransac=False, clip=False):
-    """utils/isp_algos.py:345-365, least-squares branch: non-saturation mask 1e-4 < x < 0.8 when it keeps more than
-    1 % of the points, then the line fit -- from five moment sums accumulated on the device."""
-    if ransac:
-        raise NotImplementedError("RANSAC fit (unused by YOND_SIDD.py:86)")
+def polyfit(x, y, ransac=False, clip=False, _full=False):
+    """utils/isp_algos.py:345-365: non-saturation mask 1e-4 < x < 0.8 when it keeps more than 1 % of the points, then the
+    line fit -- least squares from five moment sums accumulated on the device, or with ransac=True (:353-362) sklearn's
+    RANSACRegressor(min_samples=int(sqrt(n))) replayed on the device (ransac.hip): the subsets are drawn on the host exactly as
+    sklearn draws them after setup_seed(2024), so scikit-learn must be importable.  Returns (slope, intercept); fewer than two
+    points raise YondHipError (the reference crashes there).  `_full` adds the RANSAC internals."""
     xd, yd = _P._dev(x).reshape(-1), _P._dev(y).reshape(-1)
+    if ransac:
+        if xd.numel() != yd.numel() or xd.numel() < 2:
+            raise L.YondHipError(f"polyfit(ransac=True) needs at least 2 points, got {xd.numel()}")
+        th = torch.full((1,), float('inf'), dtype=torch.float64, device=xd.device)
+        return _P._ransac_fit(None, xd.contiguous(), yd.contiguous(), th, 1, full=_full)
     lap = torch.zeros(xd.numel(), dtype=torch.float32, device=xd.device)          # every point is below th = inf
     th = torch.full((1,), float('inf'), dtype=torch.float64, device=xd.device)
     m = _P._moments(lap, xd.contiguous(), yd.contiguous(), th).cpu().numpy()
