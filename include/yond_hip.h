@@ -821,6 +821,43 @@ size_t yond_ransac_ws_bytes(size_t n, int T);
 int yond_ransac_trials_f32(const float* x, const float* y, size_t n, const int32_t* idx, int T, int m, const float* thr2,
                            double* out, void* ws, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * M2  illuminance correction, the ELD protocol's brightness alignment before PSNR / SSIM (illum.hip; data_process/__init__.py:139-171
+ * IlluminanceCorrect.correct): p = clamp(pred, 0, 1), gain = sum(p * source) / sum(p * p) over the elements whose target is not
+ * saturated (source != 1.0f exactly: a target above 1 or a NaN target is included), out = gain * p.  Memory bound: 8 B per element
+ * read by the sums, 4 B read and 4 B written by the apply.
+ *   layout     which of four groups an element i of the flat arrays adds to:
+ *              YOND_ILLUM_BAYER    (y & 1) * 2 + (x & 1) with x = i % width, y = i / width; width and n / width even, n < 2^32
+ *              YOND_ILLUM_PACKED4  i & 3; n % 4 == 0
+ *              YOND_ILLUM_FLAT     group 0; any n > 0 (width is ignored by this layout and by PACKED4)
+ *   yond_illum_sums_f32   sums (device, float64 [5][3]): sums[g] = {num = sum p * source, den = sum p * p, count} of group g = 0..3 over
+ *       its included elements, sums[4] = (g0 + g1) + (g2 + g3), the frame's.  Every product is exact in float64 and every addition
+ *       is made in an order that depends on (n, layout, the pointers' 16-byte alignment) alone: no float64 atomics, per-workgroup
+ *       partials in ws (yond_illum_ws_bytes() bytes, 8-byte aligned) added by a second launch of one workgroup; the same call gives
+ *       the same bits.  The grid is a function of n alone: P = ceil(ceil(n / 4) / (YOND_ILLUM_BLOCK_ELEMS / 4)) workgroups up to
+ *       YOND_ILLUM_MAX_BLOCKS, above it ceil(P / ceil(P / YOND_ILLUM_MAX_BLOCKS)) of them with a stride loop (every workgroup the same
+ *       number of passes).  A NaN prediction in an included element makes its group's num and den and the total's NaN (the
+ *       clamp keeps a NaN, as torch.clamp does); under a saturated target it is left out.
+ *   yond_illum_apply_f32  out[i] = gain * clamp(pred[i], 0, 1): one float32 multiply with gain = (float)(num / den) formed on the
+ *       device from sums -- YOND_ILLUM_FRAME: row 4 (the reference's scalar); YOND_ILLUM_CFA: the row of the element's group (an
+ *       extension: per-channel black-level error).  clip != 0: then out > 1 ? 1 : out.  A NaN stays a NaN through clamp and clip.
+ *       den == 0 or an empty mask gives what IEEE gives for num / den (NaN or inf times p); nothing is special-cased.  out may be pred.
+ * 16-byte accesses when both pointers of a launch are 16-byte aligned and, under BAYER, width % 4 == 0; else one element per lane.
+ * Refused (YOND_EINVAL, nothing launched): a null pointer, a float pointer not 4-byte aligned, sums or ws not 8-byte aligned, n == 0,
+ * an unknown layout or mode, a geometry the layout does not admit. */
+#define YOND_ILLUM_BAYER 0
+#define YOND_ILLUM_PACKED4 1
+#define YOND_ILLUM_FLAT 2
+#define YOND_ILLUM_FRAME 0
+#define YOND_ILLUM_CFA 1
+#define YOND_ILLUM_MAX_BLOCKS 2048      /* the grid's cap */
+#define YOND_ILLUM_BLOCK_ELEMS 4096     /* elements a workgroup takes per pass of its stride loop (256 lanes x 4 vectors of 4) */
+size_t yond_illum_ws_bytes(void);
+int yond_illum_sums_f32(const float* pred, const float* source, size_t n, int width, int layout, double* sums /* device, [5][3] */,
+                        void* ws, void* stream);
+int yond_illum_apply_f32(const float* pred, size_t n, int width, int layout, const double* sums /* device */, int mode, int clip,
+                         float* out /* may alias pred */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -132,6 +132,9 @@ class YOND_SIDD:
         if getattr(self.parser, 'camera_noise', None) is not None:
             raise SystemExit("--camera-noise belongs to the full-frame drivers (YOND_any / YOND_ELD / YOND_LRID / YOND_DND): YOND_SIDD's block layout "
                              "(32 blocks per image, the estimate on the full frame) is a different loop and has no synthetic-noise path")
+        if getattr(self.parser, 'illum_corr', None) not in (None, 'off'):
+            raise SystemExit("--illum-corr belongs to the full-frame drivers (YOND_any / YOND_ELD / YOND_LRID): the ELD protocol's brightness alignment is "
+                             "a whole-frame step, YOND_SIDD's metrics are per block")
         self.initialization()
 
     def initialization(self):
@@ -525,6 +528,10 @@ class YONDParser:
         a.add_argument('--fit', choices=('lsq', 'ransac'), default=None, help="the line fit of the noise-level estimate: lsq, the reference's shipped least "
                        "squares (default), or ransac, its polyfit(ransac=True) replayed on the GPU (needs scikit-learn for the subset draws; frames are then "
                        "estimated one at a time, outside the device chain).  Overrides the runfile's pipeline.est_fit")
+        a.add_argument('--illum-corr', dest='illum_corr', choices=('off', 'frame', 'cfa'), default=None, help="full-frame drivers: the ELD protocol's illuminance "
+                       "correction before PSNR / SSIM -- one least-squares gain per frame between the clamped output and the unsaturated ground truth "
+                       "(frame), or one per CFA channel (cfa); the corrected metrics are reported beside the plain ones as PSNR(ic) / SSIM(ic).  Overrides "
+                       "the runfile's pipeline.illum_corr")
         from .pgnoise import synth_noise_arg
         a.add_argument('--synth-noise', dest='synth_noise', type=synth_noise_arg, default=None, metavar='K,SIGMA', help="full-frame drivers: take every item's clean "
                        "frame (hr if present, else lr) as the ground truth and make the noisy frame on the GPU, Poisson-Gaussian with system gain K and read "

@@ -33,6 +33,13 @@ code=pgrq,K=0.22,sigTL=0.76,sigGs=1.26,sigR=0.23,lam=-0.026): how far do the Poi
 banding and heavy tails.  The truth it reports is the Poisson-Gaussian level with the model's variance (camnoise.effective_pg:
 ratio * K, ratio * sigma_eff); the dark bias is a mean offset, logged and kept in `metrics[name]['bias']`, not part of the error.
 The two flags exclude each other.
+
+`--illum-corr frame | cfa` (runfile: pipeline.illum_corr) adds the ELD protocol's illuminance correction to the metrics
+(yond_public_amd/illum.py; the reference's IlluminanceCorrect, data_process/__init__.py:139-171): a frame exposed at 1 / ratio and
+multiplied back carries its black-level error as a global brightness error, which one least-squares gain against the unsaturated
+ground truth removes before PSNR / SSIM.  The plain metrics stay where they are; `psnr_ic`, `ssim_ic`, `illum_gain` and the
+`*_ic_*` means are reported beside them.  Saved frames stay uncorrected (the correction needs the ground truth); their sidecar
+carries the gain.
 """
 import os
 import time
@@ -46,6 +53,7 @@ from . import archs as _archs
 from . import camnoise as CN
 from . import data as _data
 from . import distributed as D
+from . import illum as IL
 from . import pgnoise as PG
 from . import pipeline as P
 from . import synthetic as S
@@ -107,6 +115,10 @@ class YOND_Full:
         if getattr(self.parser, 'fit', None) is not None:               # --fit overrides the runfile's pipeline.est_fit
             self.pipe['est_fit'] = self.parser.fit
         self.fit = P.est_fit_of(self.pipe)                              # 'ransac': frames take IterDenoise one at a time (stream_applies)
+        if getattr(self.parser, 'illum_corr', None) is not None:        # --illum-corr overrides the runfile's pipeline.illum_corr
+            self.pipe['illum_corr'] = self.parser.illum_corr
+        self.illum_corr = IL.illum_corr_of(self.pipe)                   # 'off' | 'frame' | 'cfa': the metrics' illuminance correction
+        self.pipe.pop('illum_corr', None)                               # (the drivers' own key: nothing of the pipeline reads it)
         if not self.pipe.get('full_dn', False):
             raise SystemExit(f"{self.parser.runfile}: the full-frame drivers run runfiles with `full_dn: True` (YOND_SIDD.py handles the block layout)")
         self.model_name, self.method_name = self.args['model_name'], self.args['method_name']
@@ -200,6 +212,8 @@ class YOND_Full:
             ds = self.dst_eval
             wp, bl = float(getattr(ds, 'wp', self.dst.get('wp', 1023))), float(getattr(ds, 'bl', self.dst.get('bl', 64)))
             sums = D.MetricSums(n_it)
+            ic_sums = D.MetricSums(n_it) if self.illum_corr != 'off' else None       # the illuminance-corrected meters
+            ic_gain_sums = [0.0] * (2 * n_it)                    # per round [sum of the frames' total gains, frames that had one]
             rel_sums = [0.0] * (4 * n_it)                        # --synth-noise: per round [sum, frames] of K's and of sigma's relative error
             device_ingest = hasattr(ds, 'raw_items') and not getattr(self.parser, 'host_ingest', False)
             if hasattr(ds, 'raw_items'):
@@ -219,6 +233,7 @@ class YOND_Full:
 
             def account(k, data, res):
                 psnrs, ssims = [], []
+                psnrs_ic, ssims_ic, ic_gains, ic_cfa = [], [], [], []
                 if data.get('hr') is not None:
                     hr = data['hr'] if isinstance(data['hr'], torch.Tensor) else torch.from_numpy(np.ascontiguousarray(data['hr'], np.float32)).to(self.device)
                     H, W = hr.shape
@@ -227,7 +242,34 @@ class YOND_Full:
                         psnrs.append(float(np.mean(ps)))
                         ssims.append(float(np.mean(ss)))
                     sums.update(psnrs, ssims)
+                    if ic_sums is not None:
+                        target = hr.clamp(0, 1)                      # (the clamp is what makes a saturated target exactly 1: left out of the gain)
+                        for it, dn in enumerate(res['raw_dns']):
+                            corrected, dev_sums = IL.illuminance_correct(dn, target, mode=self.illum_corr, clip=True)
+                            total, per_cfa, den, count = IL.gains(dev_sums)
+                            if den == 0 or count == 0 or not np.isfinite(total) or (self.illum_corr == 'cfa' and not np.isfinite(per_cfa).all()):
+                                log(f"[rank {self.rank}] warning: {data['name']} round {it}: no illuminance gain (sum p^2 = {den:g} over {count:g} "
+                                    "unsaturated targets): reported uncorrected", self.logfile)
+                                psnrs_ic.append(psnrs[it])
+                                ssims_ic.append(ssims[it])
+                            else:
+                                ps, ss = P.block_metrics(corrected, target, bh=H, bw=W)
+                                psnrs_ic.append(float(np.mean(ps)))
+                                ssims_ic.append(float(np.mean(ss)))
+                                if it < n_it:
+                                    ic_gain_sums[2 * it] += total
+                                    ic_gain_sums[2 * it + 1] += 1
+                            ic_gains.append(total)
+                            ic_cfa.append(per_cfa)
+                        ic_sums.update(psnrs_ic, ssims_ic)
+                elif ic_sums is not None and not getattr(self, '_ic_noted', False):
+                    self._ic_noted = True
+                    log(f"[rank {self.rank}] --illum-corr {self.illum_corr}: ignored for items without a reference frame (hr)", self.logfile)
                 self.metrics[data['name']] = {'psnr': psnrs, 'ssim': ssims, 'reg': res['regs']}
+                if psnrs_ic:
+                    self.metrics[data['name']].update(psnr_ic=psnrs_ic, ssim_ic=ssims_ic, illum_gain=ic_gains)
+                    if self.illum_corr == 'cfa':
+                        self.metrics[data['name']]['illum_gain_cfa'] = ic_cfa
                 true = ""
                 if self.true_level is not None:
                     # the pipeline's (K, sigma) are DN of the frame it is handed (YOND_SIDD.py:356 scales by wp - bl), digital gain
@@ -248,16 +290,29 @@ class YOND_Full:
                         bias = [float(v) * ratio for v in CN.dark_bias(self.camera_noise, self.camera_noise['code'])]
                         self.metrics[data['name']]['bias'] = bias
                         true += ", dark bias " + "/".join(f"{v:.3f}" for v in bias)
-                log(f"[rank {self.rank}] {data['name']}: " + (f"PSNR={psnrs[-1]:.2f}, SSIM={ssims[-1]:.4f}" if psnrs else "denoised (no reference frame)")
+                ic = ""
+                if psnrs_ic:
+                    ic = f", PSNR(ic)={psnrs_ic[-1]:.2f}, SSIM(ic)={ssims_ic[-1]:.4f}, gain={ic_gains[-1]:.5f}"
+                    if self.illum_corr == 'cfa':
+                        ic += " (" + "/".join(f"{v:.5f}" for v in ic_cfa[-1]) + ")"
+                log(f"[rank {self.rank}] {data['name']}: " + (f"PSNR={psnrs[-1]:.2f}, SSIM={ssims[-1]:.4f}" if psnrs else "denoised (no reference frame)") + ic
                     + f", K={res['params'][-1][0]:.3f}, sigma={res['params'][-1][1]:.3f}" + true, self.logfile)
 
             def deliver(k, data, res):
                 if callable(self.on_result):
                     self.on_result(data['name'], res)
+                info = {'rounds': [(float(q[0]), float(q[1])) for q in res['params']]}
+                if writer is not None and ic_sums is not None:
+                    # the saved frame stays uncorrected (the correction needs the ground truth); its sidecar names the last round's gain
+                    account(k, data, res)
+                    if 'illum_gain' in self.metrics[data['name']]:
+                        info['illum_gain'] = self.metrics[data['name']]['illum_gain'][-1]
+                        if self.illum_corr == 'cfa':
+                            info['illum_gain_cfa'] = self.metrics[data['name']]['illum_gain_cfa'][-1]
                 if writer is not None:                       # queued on this stream before the drivers reuse the buffer; written by the writer's threads
-                    writer.put(data['name'], res['raw_dns'][-1], (bl, wp, data.get('ratio', 1)),
-                               {'rounds': [(float(q[0]), float(q[1])) for q in res['params']]})
-                account(k, data, res)
+                    writer.put(data['name'], res['raw_dns'][-1], (bl, wp, data.get('ratio', 1)), info)
+                if writer is None or ic_sums is None:
+                    account(k, data, res)
 
             streamed = STREAM_EVAL and getattr(self.parser, 'stream', True) and not self.parser.verbose and P.stream_applies(self.pipe, self.pipe, self.biaslut)
             if streamed:
@@ -292,6 +347,17 @@ class YOND_Full:
             torch.cuda.synchronize()
             dt = D.max_over_ranks(time.perf_counter() - t0, self.device)
             red = sums.reduce(self.device)
+            ic_gain = []
+            if ic_sums is not None:
+                # one more all-reduce, only with --illum-corr: the corrected meters (MetricSums' layout: [psnr, ssim] per round, the last
+                # round's, the count) and, behind them, per round [sum of the total gains, frames that had one]
+                v = D.sum_over_ranks(ic_sums.vec.tolist() + ic_gain_sums, self.device)
+                cnt, base = v[2 * (n_it + 1)], 2 * (n_it + 1) + 1
+                if cnt:
+                    for it in range(n_it):
+                        red[f'psnr_ic_iter{it}'], red[f'ssim_ic_iter{it}'] = v[2 * it] / cnt, v[2 * it + 1] / cnt
+                    red['psnr_ic_last'], red['ssim_ic_last'] = v[2 * n_it] / cnt, v[2 * n_it + 1] / cnt
+                    ic_gain = [v[base + 2 * it] / max(v[base + 2 * it + 1], 1) for it in range(n_it)]
             if self.true_level is not None:
                 rel = D.sum_over_ranks(rel_sums, self.device)
                 for it in range(n_it):
@@ -305,10 +371,13 @@ class YOND_Full:
                 if red['count']:
                     for it in range(n_it):
                         log(f"Iter{it}: PSNR={red[f'psnr_iter{it}']:.2f}, SSIM={red[f'ssim_iter{it}']:.4f}"
+                            + (f", PSNR(ic)={red[f'psnr_ic_iter{it}']:.2f}, SSIM(ic)={red[f'ssim_ic_iter{it}']:.4f}, gain={ic_gain[it]:.5f}"
+                               if f'psnr_ic_iter{it}' in red else "")
                             + (f", fit {self.fit}: mean |K_est - K| / K = {red[f'rel_err_K_iter{it}']:.4f}" if f'rel_err_K_iter{it}' in red else "")
                             + (f", mean |sigma_est - sigma| / sigma = {red[f'rel_err_sigma_iter{it}']:.4f}" if f'rel_err_sigma_iter{it}' in red else ""),
                             self.logfile)
-                    log(f"Iter_last: PSNR={red['psnr_last']:.2f}, SSIM={red['ssim_last']:.4f}", self.logfile)
+                    log(f"Iter_last: PSNR={red['psnr_last']:.2f}, SSIM={red['ssim_last']:.4f}"
+                        + (f", PSNR(ic)={red['psnr_ic_last']:.2f}, SSIM(ic)={red['ssim_ic_last']:.4f}" if 'psnr_ic_last' in red else ""), self.logfile)
                 log(f"{len(ds)} frames on {self.world} GPU(s) in {dt:.2f} s (rank 0: {t_path / max(len(mine), 1) * 1e3:.1f} ms per frame in "
                     + ("denoise_stream + metrics, waits for the loader threads included" if streamed else "IterDenoise + metrics")
                     + f" = {npix / 1e6 / max(t_path, 1e-9):.0f} Bayer MP/s" + ("" if streamed else "; the rest is data loading") + ")", self.logfile)

@@ -142,6 +142,9 @@ PROTOTYPES = {
     "yond_ransac_absdev_f32": [vp, sz, vp, vp, vp],
     "yond_ransac_ws_bytes": [sz, i32],
     "yond_ransac_trials_f32": [vp, vp, sz, vp, i32, i32, vp, vp, vp, vp],
+    "yond_illum_ws_bytes": [],
+    "yond_illum_sums_f32": [vp, vp, sz, i32, i32, vp, vp, vp],
+    "yond_illum_apply_f32": [vp, sz, i32, i32, vp, i32, i32, vp, vp],
 }
 # experiment builds only (include/yond_hip_experiments.h): bound when the loaded library has them
 EXPERIMENT_PROTOTYPES = {
@@ -152,7 +155,8 @@ EXPERIMENT_PROTOTYPES = {
 }
 _SIZE_T_RET = {"yond_select_ws_bytes", "yond_nle_ws_bytes", "yond_lut_ws_bytes", "yond_bias_lut_big_scratch", "yond_bias_points_scratch",
                "yond_conv_wgrad_ws_bytes", "yond_conv_wgrad_split_ws_bytes",
-               "yond_est_head_ws_bytes", "yond_ransac_compact_ws_bytes", "yond_ransac_ws_bytes"}
+               "yond_est_head_ws_bytes", "yond_ransac_compact_ws_bytes", "yond_ransac_ws_bytes",
+               "yond_illum_ws_bytes"}
 
 
 class YondHipError(RuntimeError):
