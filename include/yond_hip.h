@@ -858,6 +858,44 @@ int yond_illum_sums_f32(const float* pred, const float* source, size_t n, int wi
 int yond_illum_apply_f32(const float* pred, size_t n, int width, int layout, const double* sums /* device */, int mode, int clip,
                          float* out /* may alias pred */, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * M3  residual histograms for the noise-model KL divergence (noisehist.hip; utils/sidd_utils.py:280-304 get_histogram / cal_kld): how
+ * well a noise model explains the noise of a real frame is the KL divergence between the histogram of noisy - clean and the histogram
+ * of residuals drawn from the model on the same clean frame.  The kernels count; the finish (66 numbers) is host code
+ * (yond_public_amd/noisekld.py).  B Bayer frames [B][H][W], H and W even, H * W < 2^31.  For every pixel (y, x) of frame f:
+ *     r     the residual, ONE float32 subtraction: noisy - clean (NumPy's lr - hr on float32 arrays)
+ *     c     the CFA position (y & 1) * 2 + (x & 1), the order of yond_bayer2rggb_f32
+ *     b     the intensity band: the number of thresholds[0 .. nb - 2] (float32, ascending, device; may be null when nb == 1) that are
+ *           <= clean.  A NaN clean value is in band 0.
+ *     bin   np.histogram's rule on edges[ne] (float64, ascending, device: the HOST builds them -- the reference's np.arange edges are
+ *           not -R + i * bw to the last bit): bin i holds edges[i] <= r < edges[i + 1] compared in float64, the last bin also
+ *           r == edges[ne - 1].  r outside the edges, NaN or +-inf is counted in no bin.
+ *     counts[f][b][c][bin] += 1;  counts: unsigned 64-bit [B][nb][4][ne - 1] (device), zeroed by the call.
+ *   hint_lo, hint_inv   the kernel's first guess is bin floor((r - hint_lo) * hint_inv) + 1, in float32 (edges[1] and 1 / bin width for the
+ *           reference's edges); it then walks to the bin the comparisons with the edges give.  Any values, NaN included, give the same
+ *           counts: the hint costs or saves comparisons only.
+ *   yond_noise_hist_f32     r = noisy - clean: 8 B read per pixel.
+ *   yond_pg_noise_hist_f32  r = v - clean with v the float32 value yond_pg_noise_f32 would have stored for (items[f], element index
+ *           y * W + x, clean, clip) -- same sampler, same counter -- without storing it: its counts equal, integer for integer, those of
+ *           yond_pg_noise_f32 (n_per_item = H * W) followed by yond_noise_hist_f32.
+ * The counts are integers: bit-exact whatever the schedule.  16-byte loads when the pointers are 16-byte aligned and W % 4 == 0, else
+ * one element per lane.  grid = (min(ceil(H W / YOND_NOISEHIST_BLOCK_ELEMS), cap / B), B), cap = YOND_NOISEHIST_MAX_BLOCKS, for the fused
+ * kernel YOND_NOISEHIST_MODEL_MAX_BLOCKS; every workgroup flushes its LDS histogram once, one 64-bit atomic add per non-zero bin.
+ * Refused: YOND_EINVAL for a null pointer, a misaligned pointer (4 bytes for floats, 8 for edges and counts), B outside 1..65535, odd or
+ * < 2 H or W, H * W >= 2^31, ne < 2, nb < 1, clip outside {0, 1}; YOND_EUNSUPPORTED for ne - 1 > YOND_NOISEHIST_MAX_BINS,
+ * nb > YOND_NOISEHIST_MAX_BANDS or 4 * nb * (ne - 1) > 8448 (the workgroup's LDS histogram). */
+#define YOND_NOISEHIST_MAX_BINS 256
+#define YOND_NOISEHIST_MAX_BANDS 16
+#define YOND_NOISEHIST_MAX_BLOCKS 1024    /* the grid's cap, all frames together: yond_noise_hist_f32 */
+#define YOND_NOISEHIST_MODEL_MAX_BLOCKS 6144   /* ... yond_pg_noise_hist_f32 */
+#define YOND_NOISEHIST_BLOCK_ELEMS 1024   /* pixels a workgroup takes per pass of its stride loop (256 lanes x 4) */
+int yond_noise_hist_f32(const float* noisy, const float* clean, int B, int H, int W, const double* edges /* device */, int ne,
+                        const float* thresholds /* device */, int nb, double hint_lo, double hint_inv,
+                        unsigned long long* counts /* device */, void* stream);
+int yond_pg_noise_hist_f32(const float* clean, int B, int H, int W, const YondPGItem* items /* device, [B] */, int clip,
+                           const double* edges /* device */, int ne, const float* thresholds /* device */, int nb, double hint_lo,
+                           double hint_inv, unsigned long long* counts /* device */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -135,6 +135,9 @@ class YOND_SIDD:
         if getattr(self.parser, 'illum_corr', None) not in (None, 'off'):
             raise SystemExit("--illum-corr belongs to the full-frame drivers (YOND_any / YOND_ELD / YOND_LRID): the ELD protocol's brightness alignment is "
                              "a whole-frame step, YOND_SIDD's metrics are per block")
+        if getattr(self.parser, 'noise_kld', None) is not None:
+            raise SystemExit("--noise-kld belongs to the full-frame drivers (YOND_any / YOND_ELD / YOND_LRID): the residual histogram is taken over a whole "
+                             "paired frame, YOND_SIDD's loop works on blocks")
         self.initialization()
 
     def initialization(self):
@@ -544,6 +547,16 @@ class YONDParser:
                        "g Tukey-lambda read noise of scale sigTL and shape lam -- without g Gaussian read noise sigGs --, r row noise sigR, q quantisation, "
                        "d dark bias, b shot only); optional bias=b0/b1/b2/b3, mfm=, clip=none|01|sensor.  The truth reported is the Poisson-Gaussian "
                        "level of the same variance, ratio * K and ratio * sigma_eff.  Not together with --synth-noise")
+        from .noisekld import noise_kld_arg
+        a.add_argument('--noise-kld', dest='noise_kld', type=noise_kld_arg, default=None, metavar='MODEL', help="full-frame drivers: how well a noise model "
+                       "explains every frame's noise -- the KL divergence between the histogram of noisy - clean and the histogram of residuals drawn "
+                       "from MODEL on the same clean frame (the reference's cal_kld), reported per frame as KLD, per CFA position, per intensity band, with "
+                       "the model's own sampling floor (the model against itself under a second noise key).  MODEL: est (the last round's blind "
+                       "estimate), K,SIGMA (Poisson-Gaussian, DN at capture) or cam:<a --camera-noise SPEC>.  Overrides the runfile's pipeline.noise_kld")
+        a.add_argument('--kld-range', dest='kld_range', type=float, default=None, metavar='R', help="--noise-kld: 64 bins on [-R, R] between two catch-all "
+                       "bins (default 0.1, the reference's edges).  Overrides pipeline.noise_kld_range")
+        a.add_argument('--kld-bands', dest='kld_bands', type=int, default=None, metavar='N', help="--noise-kld: split the histograms into N intensity bands of "
+                       "the clean frame, thresholds np.linspace(0, 1, N + 1)[1:-1] (default 0: none).  Overrides pipeline.noise_kld_bands")
         return a.parse_args(args)
 
 

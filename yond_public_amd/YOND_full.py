@@ -40,6 +40,14 @@ multiplied back carries its black-level error as a global brightness error, whic
 ground truth removes before PSNR / SSIM.  The plain metrics stay where they are; `psnr_ic`, `ssim_ic`, `illum_gain` and the
 `*_ic_*` means are reported beside them.  Saved frames stay uncorrected (the correction needs the ground truth); their sidecar
 carries the gain.
+
+`--noise-kld est | K,SIGMA | cam:SPEC` (runfile: pipeline.noise_kld, noise_kld_range, noise_kld_bands) reports how well a noise model
+explains each paired frame's noise (yond_public_amd/noisekld.py; the reference's cal_kld, utils/sidd_utils.py:280-304): the KL
+divergence between the histogram of lr - hr and the histogram of residuals the model draws on hr -- `est`: the last round's blind
+estimate, already in the units of the frame the pipeline is handed (exposure 1); `K,SIGMA`: a Poisson-Gaussian level in DN at capture,
+the ratio applied as --synth-noise applies it; `cam:SPEC`: the camera model of --camera-noise.  `metrics[name]` gains kld, kld_cfa (the
+four CFA positions), kld_bands (`--kld-bands N` intensity bands of hr) and kld_floor, the model against itself under a second noise key:
+the sampling noise any value has to clear.  The noise keys are crc32(name + '/kld0') and crc32(name + '/kld1').
 """
 import os
 import time
@@ -54,6 +62,7 @@ from . import camnoise as CN
 from . import data as _data
 from . import distributed as D
 from . import illum as IL
+from . import noisekld as NK
 from . import pgnoise as PG
 from . import pipeline as P
 from . import synthetic as S
@@ -119,6 +128,10 @@ class YOND_Full:
             self.pipe['illum_corr'] = self.parser.illum_corr
         self.illum_corr = IL.illum_corr_of(self.pipe)                   # 'off' | 'frame' | 'cfa': the metrics' illuminance correction
         self.pipe.pop('illum_corr', None)                               # (the drivers' own key: nothing of the pipeline reads it)
+        # --noise-kld / --kld-range / --kld-bands override the runfile's pipeline.noise_kld / noise_kld_range / noise_kld_bands
+        self.noise_kld, self.kld_range, self.kld_bands = NK.noise_kld_of(self.pipe, self.parser)
+        for key in ('noise_kld', 'noise_kld_range', 'noise_kld_bands'):
+            self.pipe.pop(key, None)
         if not self.pipe.get('full_dn', False):
             raise SystemExit(f"{self.parser.runfile}: the full-frame drivers run runfiles with `full_dn: True` (YOND_SIDD.py handles the block layout)")
         self.model_name, self.method_name = self.args['model_name'], self.args['method_name']
@@ -173,6 +186,34 @@ class YOND_Full:
         data['lr'] = PG.add_pg_noise(clean, K, sigma, wp - bl, key, [0], exposure=1.0 / float(data.get('ratio', 1)))
         return data
 
+    def model_kld(self, data, res, wp, bl):
+        """--noise-kld: {'kld', 'kld_cfa', 'kld_bands', 'kld_floor'} of one paired item -- the real residual lr - hr against the model's
+        residual on hr, and the model against itself under a second key.  One histogram pass per frame splits bands and CFA positions;
+        the marginal is their integer sum.  The Poisson-Gaussian models take the fused launch (no noisy frame is stored), the camera
+        model yond_camera_noise_f32 and then the histogram."""
+        dev = lambda t: (t if isinstance(t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(t, np.float32))).to(self.device, torch.float32).contiguous()
+        clean, noisy = dev(data['hr']), dev(data['lr'])
+        edges = NK.kld_edges(self.kld_range)
+        bands = NK.band_thresholds(self.kld_bands)
+        keys = [zlib.crc32((str(data['name']) + tag).encode()) for tag in ('/kld0', '/kld1')]
+        ratio = float(data.get('ratio', 1))
+        kind = self.noise_kld[0]
+        if kind == 'cam':
+            spec = self.noise_kld[1]
+            draw = lambda key: NK.residual_hist(CN.add_camera_noise(clean, dict(spec, wp=wp, bl=bl), spec['code'], wp - bl, key, [0], layout=CN.LAYOUT_BAYER,
+                                                                    ratio=ratio, mfm=spec['mfm'], clip=spec['clip']), clean, edges, bands)
+        else:
+            # est: (K, sigma) of the last round, DN of the frame the pipeline was handed; K,SIGMA: DN at capture, exposed at 1 / ratio
+            K, sigma, exposure = (float(res['params'][-1][0]), float(res['params'][-1][1]), 1.0) if kind == 'est' else \
+                (self.noise_kld[1], self.noise_kld[2], 1.0 / ratio)
+            if not (np.isfinite(K) and np.isfinite(sigma)):
+                return None                                      # (an estimate that is no number models nothing)
+            draw = lambda key: NK.pg_model_hist(clean, K, max(sigma, 0.0), wp - bl, key, edges, bands, exposure=exposure)
+        real, q0, q1 = NK.residual_hist(noisy, clean, edges, bands), draw(keys[0]), draw(keys[1])
+        out = NK.kld_report(real, q0, clean.numel())
+        out['kld_floor'] = NK.kld_report(q1, q0, clean.numel())['kld']
+        return out
+
     def IterDenoise(self, data, params):
         return P.IterDenoise(data['lr'], self.net, self.arch, self.pipe, p=params['p'], device=self.device,
                              log=(lambda s: log(s, self.logfile)) if self.parser.verbose else None, biaslut=self.biaslut,
@@ -215,6 +256,7 @@ class YOND_Full:
             ic_sums = D.MetricSums(n_it) if self.illum_corr != 'off' else None       # the illuminance-corrected meters
             ic_gain_sums = [0.0] * (2 * n_it)                    # per round [sum of the frames' total gains, frames that had one]
             rel_sums = [0.0] * (4 * n_it)                        # --synth-noise: per round [sum, frames] of K's and of sigma's relative error
+            kld_sums = [0.0] * 3                                 # --noise-kld: [sum of KLD, sum of the floors, frames]
             device_ingest = hasattr(ds, 'raw_items') and not getattr(self.parser, 'host_ingest', False)
             if hasattr(ds, 'raw_items'):
                 ds.raw_items = device_ingest                 # raw DN in the items, normalised on the device by the loader threads
@@ -290,13 +332,31 @@ class YOND_Full:
                         bias = [float(v) * ratio for v in CN.dark_bias(self.camera_noise, self.camera_noise['code'])]
                         self.metrics[data['name']]['bias'] = bias
                         true += ", dark bias " + "/".join(f"{v:.3f}" for v in bias)
+                kld = ""
+                paired = data.get('hr') is not None and data.get('lr') is not None
+                rep = self.model_kld(data, res, wp, bl) if self.noise_kld is not None and paired else None
+                if rep is not None:
+                    self.metrics[data['name']].update(rep)
+                    kld_sums[0] += rep['kld']
+                    kld_sums[1] += rep['kld_floor']
+                    kld_sums[2] += 1
+                    kld = f", KLD={rep['kld']:.3e} (cfa " + "/".join(f"{v:.3e}" for v in rep['kld_cfa']) + ")"
+                    if len(rep['kld_bands']) > 1:
+                        kld += " (bands " + "/".join(f"{v:.3e}" for v in rep['kld_bands']) + ")"
+                    kld += f", KLD floor={rep['kld_floor']:.3e}"
+                elif self.noise_kld is not None and paired:
+                    log(f"[rank {self.rank}] warning: {data['name']}: the estimate K={res['params'][-1][0]}, sigma={res['params'][-1][1]} is not finite: no KLD",
+                        self.logfile)
+                elif self.noise_kld is not None and not getattr(self, '_kld_noted', False):
+                    self._kld_noted = True
+                    log(f"[rank {self.rank}] --noise-kld: ignored for items without a reference frame (hr)", self.logfile)
                 ic = ""
                 if psnrs_ic:
                     ic = f", PSNR(ic)={psnrs_ic[-1]:.2f}, SSIM(ic)={ssims_ic[-1]:.4f}, gain={ic_gains[-1]:.5f}"
                     if self.illum_corr == 'cfa':
                         ic += " (" + "/".join(f"{v:.5f}" for v in ic_cfa[-1]) + ")"
                 log(f"[rank {self.rank}] {data['name']}: " + (f"PSNR={psnrs[-1]:.2f}, SSIM={ssims[-1]:.4f}" if psnrs else "denoised (no reference frame)") + ic
-                    + f", K={res['params'][-1][0]:.3f}, sigma={res['params'][-1][1]:.3f}" + true, self.logfile)
+                    + f", K={res['params'][-1][0]:.3f}, sigma={res['params'][-1][1]:.3f}" + true + kld, self.logfile)
 
             def deliver(k, data, res):
                 if callable(self.on_result):
@@ -365,6 +425,10 @@ class YOND_Full:
                         red[f'rel_err_K_iter{it}'] = rel[4 * it] / rel[4 * it + 1]
                     if rel[4 * it + 3]:
                         red[f'rel_err_sigma_iter{it}'] = rel[4 * it + 2] / rel[4 * it + 3]
+            if self.noise_kld is not None:
+                v = D.sum_over_ranks(kld_sums, self.device)      # one more all-reduce, only with --noise-kld
+                if v[2]:
+                    red['kld'], red['kld_floor'] = v[0] / v[2], v[1] / v[2]
             results[label] = red
             if self.rank == 0:
                 log(f'{self.method_name} [{label}]: {len(ds)} frames', self.logfile)
@@ -378,6 +442,8 @@ class YOND_Full:
                             self.logfile)
                     log(f"Iter_last: PSNR={red['psnr_last']:.2f}, SSIM={red['ssim_last']:.4f}"
                         + (f", PSNR(ic)={red['psnr_ic_last']:.2f}, SSIM(ic)={red['ssim_ic_last']:.4f}" if 'psnr_ic_last' in red else ""), self.logfile)
+                if 'kld' in red:
+                    log(f"Noise model {self.noise_kld[0]}: mean KLD={red['kld']:.3e}, mean KLD floor={red['kld_floor']:.3e}", self.logfile)
                 log(f"{len(ds)} frames on {self.world} GPU(s) in {dt:.2f} s (rank 0: {t_path / max(len(mine), 1) * 1e3:.1f} ms per frame in "
                     + ("denoise_stream + metrics, waits for the loader threads included" if streamed else "IterDenoise + metrics")
                     + f" = {npix / 1e6 / max(t_path, 1e-9):.0f} Bayer MP/s" + ("" if streamed else "; the rest is data loading") + ")", self.logfile)

@@ -8,26 +8,10 @@
 // safe: a thread reads the elements it writes before it writes them and nobody else touches them.
 // grid = (min(ceil(groups / 256), PG_MAX_BLOCKS), B), grid-stride over the groups of one item.
 #include "common.h"
-#include "pgnoise_sampler.h"
+#include "pgnoise_element.h"
 
 #define PG_T 256
 #define PG_MAX_BLOCKS (1 << 20)
-
-__device__ __forceinline__ float pg_element(const YondPGItem& it, uint64_t index, float x, int clip) {
-    if (!(fabsf(x) <= 3.402823466e38f)) return __builtin_nanf("");        // NaN, +-inf
-    const float e = it.exposure, beta1 = it.beta1;
-    const float xp = fmaxf(x, 0.0f);
-    const bool shot = beta1 > 0.0f;
-    float lam = shot ? xp * e / beta1 : 0.0f;
-    const bool huge = !(lam <= 3.402823466e38f);                            // x e / beta1 overflowed: the count is not representable,
-    if (huge) lam = 0.0f;                                                   // its relative noise is nil
-    const PGDraw d = pg_draw(it.key, it.slot, index, lam);
-    const float signal = (shot && !huge) ? (d.k * beta1) / e : xp;
-    float y = signal + fminf(x, 0.0f) + it.sigma_n * d.z / e;
-    y = fminf(fmaxf(y, -3.402823466e38f), 3.402823466e38f);                // a finite x never gives an infinity
-    if (clip) y = fminf(fmaxf(y, 0.0f), 1.0f);
-    return y;
-}
 
 // clean and noisy carry no __restrict__: they may be the same pointer
 __global__ __launch_bounds__(PG_T) void pg_noise_kernel(const float* clean, float* noisy, size_t n, const YondPGItem* __restrict__ items,

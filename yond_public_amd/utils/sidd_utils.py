@@ -1,10 +1,11 @@
-"""Function seam of utils/sidd_utils.py for the path: rot_bayer (:198-213), the SIDD metadata reader (:3-73) and the sRGB
-renderer process_sidd_image (:156-180)."""
+"""Function seam of utils/sidd_utils.py for the path: rot_bayer (:198-213), the SIDD metadata reader (:3-73), the sRGB
+renderer process_sidd_image (:156-180) and the noise-model KLD get_histogram / cal_kld (:280-304, counted on the device: noisekld.py)."""
 import numpy as np
 import torch
 
 from .. import _lib as L
 from .. import pipeline as _P
+from ..noisekld import cal_kld, get_histogram  # noqa: F401  (where the reference keeps them)
 
 _ROT_K = {((1, 2), (2, 3)): 0, ((2, 1), (3, 2)): 3, ((2, 3), (1, 2)): 1, ((3, 2), (2, 1)): 2}     # utils/sidd_utils.py:199-206
 
