@@ -61,6 +61,8 @@ K1_SUB2 = True                      # the decoder GEMMs with two sub-positions p
 K1_D2_LEVELS = (3,)                 # decoder levels whose GEMM also stores SiLU(x) in split planes for the block's conv1 (YondConvDesc.dst2), as the stride-2
                                     # layers do from SP_CONV1_MIN_LEVEL down.  Measured per (GEMM + conv1) pair, two runs each (tools/layer_times.py, K1_D2_LEVELS=...):
                                     # level 3 274 -> 254-262 us, level 2 302 -> 293-303, level 1 362 -> 357-361: kept where it is clear of the noise.  () = off
+K1_STATIONARY_LEVELS = (2, 1, 0)    # decoder levels (of the GEMM's output: 2 = the GEMM 3 -> 2) whose GEMM runs with stationary weights and pixels loaded straight into
+                                    # registers (descriptor algo 6, csrc/gemm_k1_stationary.hip) where the library takes the descriptor; bit-identical to the template.  () = off
 K1_D2_LEVELS_HALF = ()              # ... on the fp16 path's h-only flow: none (the GEMM takes its 128-column tile instead, which has no second output)
 SP_CONV1_MIN_LEVEL = 3              # from this level down a stride-2 layer also stores SiLU(x) in split planes (YondConvDesc.dst2), so that the
                                     # next block's conv1 stages by LDS-DMA alone (there conv1 would repeat the SiLU + split per output-channel tile)
@@ -377,7 +379,7 @@ class DenoiserPlan:
         return cache[k]
 
     def _conv(self, pc, src0, src1, N, H, W, dst, escale=None, eshift=None, ebatch=0, res=None, pre_act=0, post_act=0,
-              slope=0.0, algo=None, out4=None, in_fmt=0, out_fmt=0, res_fmt=0, dst2=None):
+              slope=0.0, algo=None, out4=None, in_fmt=0, out_fmt=0, res_fmt=0, dst2=None, stationary=False):
         d = L.YondConvDesc()
         d.src0 = src0.data_ptr()
         d.src1 = src1.data_ptr() if src1 is not None else None
@@ -445,12 +447,14 @@ class DenoiserPlan:
         d.status = status.data_ptr() + 4 * self.status_slot if status is not None else None
         d.in_fmt, d.out_fmt, d.res_fmt = in_fmt, out_fmt, res_fmt
         d.dst2 = dst2.data_ptr() if dst2 is not None else None
-        if SNAKE_ORDER and d.algo in (3, 4):
+        if stationary and d.algo == 3 and self.lib.yond_gemm_k1_stationary_supported(C.byref(d)):
+            d.algo = 6                                   # the decoder GEMM with stationary weights; every other descriptor keeps the template
+        if SNAKE_ORDER and d.algo in (3, 4, 6):
             self._tile_order = 1 - getattr(self, '_tile_order', 0)      # (the first layer, conv_in, runs first row to last)
             d.tile_order = self._tile_order
         clk = getattr(self, 'clk', None)             # bench.py: in-kernel clock of the split-operand launches (int64[2] on the device)
-        d.clk = clk.data_ptr() if (clk is not None and d.algo in (3, 4)) else None
-        if (in_fmt or out_fmt or res_fmt) and d.algo not in (3, 4):
+        d.clk = clk.data_ptr() if (clk is not None and d.algo in (3, 4, 6)) else None
+        if (in_fmt or out_fmt or res_fmt) and d.algo not in (3, 4, 6):
             raise L.YondHipError("split-plane / 4-channel-plane tensors need the split-operand kernel (algo 3, or 4 with h-only planes)")
         if out4 is not None:
             # (w [4][Cout], bias [4], network input NHWC4 or None, per-image maxima or None, destination NHWC4)
@@ -464,8 +468,8 @@ class DenoiserPlan:
         prof = getattr(self, 'prof', None)
         if prof is not None:
             tag = f"conv_wino_kernel<{tn}>" if d.algo == 1 else f"conv_mfma_kernel<{pc.ksize},{pc.stride},8,{tn},{kc}>"
-            if d.algo in (3, 4):
-                tag = f"conv_split_kernel<{pc.stride if pc.ksize == 3 else 'k1'},{tn},{5 - d.algo}>"
+            if d.algo in (3, 4, 6):              # (algo 6: the layer and arithmetic of algo 3 -- the split family's tag, marked as the stationary-weight kernel)
+                tag = f"conv_split_kernel<{pc.stride if pc.ksize == 3 else 'k1'},{tn},{1 if d.algo == 4 else 2}>" + ("/stationary" if d.algo == 6 else "")
             if d.algo == 2:
                 tag += "/f16"
             if d.algo == 5:
@@ -643,7 +647,8 @@ class DenoiserPlan:
                     # (decoder level of block i = 9 - i; images too narrow for the unfolded GEMM keep the folded kernels, which have no second output)
                     xsp = (self._new_sp(('xspd', i), N, 2 * h, 2 * w, cp, pt)
                            if (flow and not last and (9 - i) in (K1_D2_LEVELS if pt == 2 else K1_D2_LEVELS_HALF) and up is blk['upsc'] and cp % 64 == 0 and w > 16) else None)     # (the dispatcher's second output: 64-wide tiles, conv_split.hip)
-                    self._conv(up, cur, skips[10 - i], N, h, w, xs, in_fmt=SP if flow else 0, out_fmt=xfmt, dst2=xsp)
+                    self._conv(up, cur, skips[10 - i], N, h, w, xs, in_fmt=SP if flow else 0, out_fmt=xfmt, dst2=xsp,
+                               stationary=(9 - i) in K1_STATIONARY_LEVELS)
                     h, w = 2 * h, 2 * w
                     cur = xs
                 # z = conv2(SiLU(FiLM(conv1(SiLU(x))))) + x : the first SiLU runs in conv1's staging (x has other readers); the
