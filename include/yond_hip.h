@@ -172,7 +172,10 @@ typedef struct YondConvDesc {
                              planes in; shuffle 1 with planes of 4 out, or shuffle 2 at 32-channel output pixels with [N][H][W][C] out;
                              the same packed weights, the same bits) with the channel
                              tile's weights stationary in LDS and the pixels loaded straight into registers -- only for a descriptor
-                             yond_gemm_k1_stationary_supported accepts, YOND_EUNSUPPORTED otherwise */
+                             yond_gemm_k1_stationary_supported accepts, YOND_EUNSUPPORTED otherwise; 7 the 3x3 stride-2 layer of algo 3
+                             (split planes in, planes of 4 out, with or without dst2; the same packed weights, the same bits) on 8-row
+                             tiles, two output rows per wave, one input image in LDS (csrc/conv_s2_tall.hip) -- only for a descriptor
+                             yond_conv_s2_tall_supported accepts, YOND_EUNSUPPORTED otherwise */
     /* Fused output projection (archs/Unet.py:466-470 `conv10` + residual + data_inv_normalize, i.e. what yond_conv_out_f32
        does as a kernel of its own): when out4_dst is set the convolution must produce ONE 32-channel tile (Cout = tn = 32,
        algo 3, stride 1); its result v is not stored (dst may be NULL) and out4_dst[n][y][x][c] =
@@ -265,6 +268,8 @@ int yond_conv_split_supported(int ksize, int stride, int cin, int cout);
 int yond_pack_conv_split_weight_f32(const float* w, int cout, int cin, int ksize, int tn, int parts, float* dst);
 /* 1 if the decoder GEMM described by `desc` (filled in for algo 3) may run with algo = 6 instead (csrc/gemm_k1_stationary.hip), else 0. */
 int yond_gemm_k1_stationary_supported(const YondConvDesc* desc);
+/* 1 if the stride-2 layer described by `desc` (filled in for algo 3) may run with algo = 7 instead (csrc/conv_s2_tall.hip), else 0. */
+int yond_conv_s2_tall_supported(const YondConvDesc* desc);
 /* The same packing on the device (w and dst are device pointers; asynchronous on `stream`): the training step re-packs the
  * weights it has just updated without a host round trip.  A weight outside fp16's range sets bit 0 of *status (device int,
  * may be NULL) instead of failing the call. */

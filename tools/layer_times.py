@@ -9,6 +9,8 @@ if os.environ.get("K1_D2_LEVELS") is not None:
     E.K1_D2_LEVELS = tuple(int(v) for v in os.environ["K1_D2_LEVELS"].split(",") if v)
 if os.environ.get("K1_STATIONARY_LEVELS") is not None:     # decoder levels on the stationary-weight GEMM ("" = none: the template everywhere)
     E.K1_STATIONARY_LEVELS = tuple(int(v) for v in os.environ["K1_STATIONARY_LEVELS"].split(",") if v)
+if os.environ.get("S2_TALL_LEVELS") is not None:            # levels (of the layer's input) whose stride-2 layer runs on 8-row tiles ("" = none)
+    E.S2_TALL_LEVELS = tuple(int(v) for v in os.environ["S2_TALL_LEVELS"].split(",") if v)
 if os.environ.get("K1_D2_LEVELS_HALF") is not None:
     E.K1_D2_LEVELS_HALF = tuple(int(v) for v in os.environ["K1_D2_LEVELS_HALF"].split(",") if v)
 if os.environ.get("SP_CONV1_MIN_LEVEL"):            # A/B of the engine's data-flow constant (tools only)

@@ -65,6 +65,7 @@ PROTOTYPES = {
     "yond_conv_split_supported": [i32, i32, i32, i32],
     "yond_pack_conv_split_weight_f32": [vp, i32, i32, i32, i32, i32, vp],
     "yond_gemm_k1_stationary_supported": [C.POINTER(YondConvDesc)],
+    "yond_conv_s2_tall_supported": [C.POINTER(YondConvDesc)],
     "yond_pack_conv_split_weight_dev_f32": [vp, i32, i32, i32, i32, i32, vp, vp, vp],
     "yond_pack_conv_split_weights_batch_dev_f32": [vp, vp, i32, vp, sz, vp, vp],
     "yond_conv_in_f32": [vp, vp, i32, i32, i32, i32, vp, vp, f32, vp, i32, vp],

@@ -632,6 +632,7 @@ extern "C" int yond_pack_conv_weight_split_f32(const float* w, int cout, int cin
 int yond_conv_wino_dispatch(const YondConvDesc& d, hipStream_t st);      // conv_wino.hip
 int yond_conv_split_dispatch(const YondConvDesc& d, hipStream_t st);     // conv_split.hip
 int yond_gemm_k1_stationary_dispatch(const YondConvDesc& d, hipStream_t st);   // gemm_k1_stationary.hip
+int yond_conv_s2_tall_dispatch(const YondConvDesc& d, hipStream_t st);         // conv_s2_tall.hip
 
 extern "C" int yond_conv2d_f32(const YondConvDesc* dp, void* stream) {
     if (!dp) return YOND_EINVAL;
@@ -646,6 +647,7 @@ extern "C" int yond_conv2d_f32(const YondConvDesc* dp, void* stream) {
     if (d.pre_act != 0 && d.pre_act != 1) return YOND_EINVAL;
     if (d.in_fmt < 0 || d.in_fmt > 2 || d.out_fmt < 0 || d.out_fmt > 2 || (d.res_fmt != 0 && d.res_fmt != 2)) return YOND_EINVAL;
     if (d.algo == 6) return yond_gemm_k1_stationary_dispatch(d, st);          // the decoder GEMM with stationary weights: refuses what it does not take
+    if (d.algo == 7) return yond_conv_s2_tall_dispatch(d, st);                // the stride-2 layer on 8-row tiles, two output rows per wave: likewise
     if ((d.in_fmt || d.out_fmt || d.res_fmt) && d.algo != 3 && d.algo != 4) return YOND_EUNSUPPORTED;       // other formats: the split-operand kernel only (algo 4: h-only planes)
     if (d.algo == 1) return yond_conv_wino_dispatch(d, st);
     if (d.algo == 3 || d.algo == 4) return yond_conv_split_dispatch(d, st);

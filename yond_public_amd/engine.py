@@ -63,6 +63,9 @@ K1_D2_LEVELS = (3,)                 # decoder levels whose GEMM also stores SiLU
                                     # level 3 274 -> 254-262 us, level 2 302 -> 293-303, level 1 362 -> 357-361: kept where it is clear of the noise.  () = off
 K1_STATIONARY_LEVELS = (2, 1, 0)    # decoder levels (of the GEMM's output: 2 = the GEMM 3 -> 2) whose GEMM runs with stationary weights and pixels loaded straight into
                                     # registers (descriptor algo 6, csrc/gemm_k1_stationary.hip) where the library takes the descriptor; bit-identical to the template.  () = off
+S2_TALL_LEVELS = (0, 1, 2)          # levels (of the layer's INPUT: 0 = the layer 0 -> 1) whose stride-2 layer runs on 8-row tiles, two output rows per wave, one input image in
+                                    # LDS (descriptor algo 7, csrc/conv_s2_tall.hip) where the library takes the descriptor; bit-identical to the template.  () = off
+                                    # (level 3, the layer 3 -> 4: 384 tiles of 8 rows are 1.5 rounds of 256 workgroups -- 13.5 us slower than the template at the cfg-2 shape: off; profiles/s2_tall_ab.txt)
 K1_D2_LEVELS_HALF = ()              # ... on the fp16 path's h-only flow: none (the GEMM takes its 128-column tile instead, which has no second output)
 SP_CONV1_MIN_LEVEL = 3              # from this level down a stride-2 layer also stores SiLU(x) in split planes (YondConvDesc.dst2), so that the
                                     # next block's conv1 stages by LDS-DMA alone (there conv1 would repeat the SiLU + split per output-channel tile)
@@ -379,7 +382,7 @@ class DenoiserPlan:
         return cache[k]
 
     def _conv(self, pc, src0, src1, N, H, W, dst, escale=None, eshift=None, ebatch=0, res=None, pre_act=0, post_act=0,
-              slope=0.0, algo=None, out4=None, in_fmt=0, out_fmt=0, res_fmt=0, dst2=None, stationary=False):
+              slope=0.0, algo=None, out4=None, in_fmt=0, out_fmt=0, res_fmt=0, dst2=None, stationary=False, s2_tall=False):
         d = L.YondConvDesc()
         d.src0 = src0.data_ptr()
         d.src1 = src1.data_ptr() if src1 is not None else None
@@ -449,12 +452,14 @@ class DenoiserPlan:
         d.dst2 = dst2.data_ptr() if dst2 is not None else None
         if stationary and d.algo == 3 and self.lib.yond_gemm_k1_stationary_supported(C.byref(d)):
             d.algo = 6                                   # the decoder GEMM with stationary weights; every other descriptor keeps the template
-        if SNAKE_ORDER and d.algo in (3, 4, 6):
+        if s2_tall and d.algo == 3 and pc.ksize == 3 and pc.stride == 2 and self.lib.yond_conv_s2_tall_supported(C.byref(d)):
+            d.algo = 7                                   # the stride-2 layer on 8-row tiles; folded levels, h-only planes, [N][H][W][C] tensors keep the template
+        if SNAKE_ORDER and d.algo in (3, 4, 6, 7):
             self._tile_order = 1 - getattr(self, '_tile_order', 0)      # (the first layer, conv_in, runs first row to last)
             d.tile_order = self._tile_order
         clk = getattr(self, 'clk', None)             # bench.py: in-kernel clock of the split-operand launches (int64[2] on the device)
-        d.clk = clk.data_ptr() if (clk is not None and d.algo in (3, 4, 6)) else None
-        if (in_fmt or out_fmt or res_fmt) and d.algo not in (3, 4, 6):
+        d.clk = clk.data_ptr() if (clk is not None and d.algo in (3, 4, 6, 7)) else None
+        if (in_fmt or out_fmt or res_fmt) and d.algo not in (3, 4, 6, 7):
             raise L.YondHipError("split-plane / 4-channel-plane tensors need the split-operand kernel (algo 3, or 4 with h-only planes)")
         if out4 is not None:
             # (w [4][Cout], bias [4], network input NHWC4 or None, per-image maxima or None, destination NHWC4)
@@ -468,8 +473,8 @@ class DenoiserPlan:
         prof = getattr(self, 'prof', None)
         if prof is not None:
             tag = f"conv_wino_kernel<{tn}>" if d.algo == 1 else f"conv_mfma_kernel<{pc.ksize},{pc.stride},8,{tn},{kc}>"
-            if d.algo in (3, 4, 6):              # (algo 6: the layer and arithmetic of algo 3 -- the split family's tag, marked as the stationary-weight kernel)
-                tag = f"conv_split_kernel<{pc.stride if pc.ksize == 3 else 'k1'},{tn},{1 if d.algo == 4 else 2}>" + ("/stationary" if d.algo == 6 else "")
+            if d.algo in (3, 4, 6, 7):           # (algo 6 / 7: the layer and arithmetic of algo 3 -- the split family's tag, marked as the stationary-weight / 8-row kernel)
+                tag = f"conv_split_kernel<{pc.stride if pc.ksize == 3 else 'k1'},{tn},{1 if d.algo == 4 else 2}>" + ("/stationary" if d.algo == 6 else "/tall" if d.algo == 7 else "")
             if d.algo == 2:
                 tag += "/f16"
             if d.algo == 5:
@@ -669,7 +674,7 @@ class DenoiserPlan:
                         skips[i] = cur
                         nxt = self._new(N, h // 2, w // 2, blk['pool'].coutp)
                         xsp = self._new_sp(('xsp', i + 1), N, h // 2, w // 2, blk['pool'].coutp, pt) if (flow and i >= SP_CONV1_MIN_LEVEL) else None
-                        self._conv(blk['pool'], cur, None, N, h, w, nxt, in_fmt=SP, out_fmt=P4, dst2=xsp)
+                        self._conv(blk['pool'], cur, None, N, h, w, nxt, in_fmt=SP, out_fmt=P4, dst2=xsp, s2_tall=(i - 1) in S2_TALL_LEVELS)   # (level of block i = i - 1)
                         h, w = h // 2, w // 2
                         cur = nxt
                         continue
@@ -704,7 +709,7 @@ class DenoiserPlan:
                     skips[i] = cur
                     nxt = self._new(N, h // 2, w // 2, blk['pool'].coutp)
                     xsp = self._new_sp(('xsp', i + 1), N, h // 2, w // 2, blk['pool'].coutp, pt) if (flow and i >= SP_CONV1_MIN_LEVEL) else None   # (level of block i + 1 = i)
-                    self._conv(blk['pool'], cur, None, N, h, w, nxt, in_fmt=SP if flow else 0, out_fmt=P4 if flow else 0, dst2=xsp)
+                    self._conv(blk['pool'], cur, None, N, h, w, nxt, in_fmt=SP if flow else 0, out_fmt=P4 if flow else 0, dst2=xsp, s2_tall=(i - 1) in S2_TALL_LEVELS)
                     h, w = h // 2, w // 2
                     cur = nxt
             feat = cur
