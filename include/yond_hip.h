@@ -907,6 +907,42 @@ int yond_pg_noise_hist_f32(const float* clean, int B, int H, int W, const YondPG
                            const double* edges /* device */, int ne, const float* thresholds /* device */, int nb, double hint_lo,
                            double hint_inv, unsigned long long* counts /* device */, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * I4  clean raw frames -> raw training pairs (rawcrop.hip; memory bound, 2 B in + 8 B out per output)
+ * Replaces data_process/yond_datasets.py:153-212 (one item of SID_Raw_Dataset: DN normalisation, Bayer-pattern rotation, packing,
+ * clip, square-root augmentation, crops, brightness / white-balance jitter, AWGN) for B patches of one side in one call.
+ *   frames     uint16 (dtype 0) or float32 DN (dtype 1) [..][H][W] Bayer frames (device), frames_len elements in all; patch b reads
+ *              the frame that starts at element patches[b].frame
+ *   patches    YondRawCropPatch [B] on the HOST: read and checked before anything is launched, then handed to the kernel by value
+ *              (RC_CHUNK = 64 patches per launch; a batch of up to 64 is one launch).  The array is free again when the call returns.
+ *   hr, lr     float32 [B][4][ps][ps] (device); sigma float32 [B] (device): sigma[b] = patches[b].sigma
+ * Output element hr[b][c][y][x], c = 2 dy + dx (bayer2rggb): the rotated frame is np.rot90(frame, pattern) of (H, W) or (W, H), its
+ * packed position (y0 + y, x0 + x) and sub-site (dy, dx) name one source pixel DN.  In float32, every step rounded once:
+ *     v = (float(DN) - bl) / (wp - bl)        true subtract and divide
+ *     v = min(max(v, 0), 1);  v = sqrt(v) if vst_aug;  v = v * rgb_gain
+ *     c == 0: v = float(double(v) * gain0);   c == 2: v = float(double(v) * gain2)       (the reference's float32 plane times a
+ *                                                                                          float64 ratio, stored to float32)
+ *     hr = v;  lr = v + z * sigma
+ * z is standard normal: Philox4x32-10 keyed by (key, slot), counter = (element index in the patch) / 4, Box-Muller; element
+ * index % 4 picks one of the call's four normals.  lr[b] is a function of (patches[b], element) alone.  clip != 0 clamps hr and lr
+ * to [0, 1].  DN must be finite.  16-byte stores when hr and lr are 16-byte aligned, 4-byte stores otherwise: same values.
+ * Refused (YOND_EINVAL, nothing launched, nothing written): a null pointer, H or W odd or < 2, B < 1, ps < 1 or > 16384, a dtype other
+ * than 0 / 1, wp <= bl, and for any patch a pattern outside 0..3, a vst_aug outside {0, 1}, a crop that leaves the rotated frame
+ * (y0 < 0, x0 < 0, y0 + ps > h', x0 + ps > w'), frame < 0 or frame + H * W > frames_len. */
+typedef struct {
+    long long frame;        /* first element of the Bayer frame in `frames` */
+    int y0, x0;             /* crop origin in PACKED coordinates of the ROTATED frame */
+    int pattern;            /* k of np.rot90(bayer, k, axes=(-2,-1)), 0..3 */
+    int vst_aug;            /* 1: hr = sqrt(hr) after the [0,1] clip */
+    float rgb_gain;         /* 1 when the item draws no gains */
+    double gain0, gain2;    /* multipliers of packed channels 0 and 2; 1 when none */
+    float sigma;
+    unsigned key, slot;     /* noise stream */
+} YondRawCropPatch;         /* 64 bytes */
+int yond_rawcrop_f32(const void* frames, size_t frames_len, int dtype /*0 u16, 1 f32*/, int H, int W, float bl, float wp,
+                     const YondRawCropPatch* patches, int B, int ps /* packed patch side */, int clip, float* hr, float* lr,
+                     float* sigma, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,16 @@ assert PATCH_DTYPE.itemsize == 72
 
 
 # -- metadata ------------------------------------------------------------------------------------------------------------------
+def random_gains(gen=None):
+    """unprocess.py:50-59 on `gen`: rand(1), the normal, red, blue, in that order.  (rgb_gain, red, blue), (1,) float32 tensors."""
+    bright = torch.rand(1, generator=gen) < 0.9
+    n = torch.normal(torch.tensor([0.8]), torch.tensor([0.1]), generator=gen)
+    rgb_gain = 1.0 / n if bright else 0.2 / n
+    red = torch.empty(1).uniform_(1.4, 2.5, generator=gen)
+    blue = torch.empty(1).uniform_(1.5, 2.4, generator=gen)
+    return rgb_gain, red, blue
+
+
 def sample_meta(gen, lock_wb=False):
     """unprocess.py:180-183 on `gen`: rgb2cam (random_ccm, :7-47), then the gains (random_gains, :50-59) unless lock_wb is a
     [rgb_gain, red, blue] triple.  The draws are the reference's, in its order: 4 weights, rand(1), normal, red, blue.
@@ -41,11 +51,7 @@ def sample_meta(gen, lock_wb=False):
     rgb2cam = torch.mm(xyz2cam, torch.tensor(RGB2XYZ))
     rgb2cam = rgb2cam / torch.sum(rgb2cam, dim=-1, keepdim=True)
     if lock_wb is False or lock_wb is None:
-        bright = torch.rand(1, generator=gen) < 0.9
-        n = torch.normal(torch.tensor([0.8]), torch.tensor([0.1]), generator=gen)
-        rgb_gain = 1.0 / n if bright else 0.2 / n
-        red = torch.empty(1).uniform_(1.4, 2.5, generator=gen)
-        blue = torch.empty(1).uniform_(1.5, 2.4, generator=gen)
+        rgb_gain, red, blue = random_gains(gen)
     else:
         rgb_gain, red, blue = torch.tensor(np.asarray(lock_wb, np.float32)).reshape(3, 1)
     return {'rgb2cam': rgb2cam, 'cam2rgb': torch.inverse(rgb2cam), 'rgb_gain': rgb_gain, 'red': red, 'blue': blue}

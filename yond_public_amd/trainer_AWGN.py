@@ -12,7 +12,7 @@ over RCCL in 25 MB buckets behind the backward pass (distributed.GradReducer) in
 shard of the epoch's permutation (DistributedSampler's rule), and the evaluation forward is the inference engine.
 
 Data: a dataset directory (`<root_dir>/<mode>[_<subname>]/*.npy`; DIV2K_Img2Raw_Dataset also `<root_dir>/npy/<mode>`, the
-reference's layout) holds one of two kinds of patch.
+reference's layout) holds one of two kinds of patch, or a set of whole raw frames.
   - sRGB crops, (H, W, 3) uint8 / uint16, the reference's training sets: each batch is synthesised on the GPU in one launch
     (yond_public_amd/img2raw.py, csrc/img2raw.hip) -- unprocess (random CCM, gains, gain mask), mosaic, Bayer-pattern rotation
     and Gaussian noise, yond_datasets.py:277-334 -- from a device cache of the crops.  Metadata, pattern and sigma are drawn on
@@ -21,11 +21,18 @@ reference's layout) holds one of two kinds of patch.
   - patches ALREADY packed raw, each (4, h, w) or (h, w, 4) float in [0, 1], with the reference's noise model on top on the host
     (yond_datasets.py:308-320: sigma log-uniform in [sigma_min, sigma_max] / 255 when training, the fixed `dst_eval.sigma` with a
     per-index seed otherwise; Bayer-pattern augmentation by rotating the mosaic, :296-303).
+  - whole clean raw frames, (H, W) uint16 or float32 DN, for `dataset: SID_Raw_Dataset` (yond_datasets.py:46-212), listed by the
+    reference's infos/SID_<mode>.info or found as <root_dir>/<mode>/*.npy: the frames stay on the device as stored and each batch
+    -- batch_size frames x crop_per_image patches -- is cut from them in one launch (yond_public_amd/rawcrop.py,
+    csrc/rawcrop.hip): DN normalisation, Bayer-pattern rotation, square-root augmentation of the ground truth, random or
+    non-overlapped crops, brightness / white-balance jitter and Gaussian noise.  Evaluation item k is the whole frame with pattern
+    k % 4, vst_aug (k // 4) % 2 (the reference's is unseeded), the reference's gains after setup_seed(k) and noise key k; a frame's
+    white balance is the file's every time (the reference lets it drift).  `--synthetic N` makes N seeded frames.
 DIV2K_PG_Dataset (yond_datasets.py:661-764) takes sRGB crops only and puts signal-dependent noise on them: (K, sigma) per training
 item from the reference's camera-noise prior, noisy = Poisson(x / beta1) beta1 + N(0, beta2) in one more launch
 (yond_public_amd/pgnoise.py, csrc/pgnoise.hip); every evaluation item gets `dst_eval.K` / `dst_eval.sigma_dn` (or `--synth-noise
 K,SIGMA`), else the prior's draw on RandomState(0).  Its `command: est` branch and guided architectures are refused.
-A directory mixing the two is refused before the first step.  Without data the trainer draws seeded synthetic patches so that
+A directory mixing the first two is refused before the first step.  Without data the trainer draws seeded synthetic patches so that
 the loop can be exercised and timed.  Plots, FastISP previews (the function itself: utils/isp_ops.FastISP) and the consistency branch (`command: consistency`) are not wired in.
 """
 import argparse
@@ -43,6 +50,7 @@ from . import archs as _archs
 from . import distributed as D
 from . import img2raw as I
 from . import pgnoise as PG
+from . import rawcrop as R
 from . import synthetic as S
 from . import train as T
 from .YOND_SIDD import log
@@ -188,13 +196,75 @@ class DIV2K_PG_Dataset(DIV2K_Img2Raw_Dataset):
         raise NotImplementedError("DIV2K_PG_Dataset items are made on the GPU (pgnoise.PGSource), not on the host")
 
 
+class SID_Raw_Dataset:
+    """yond_datasets.py:46-212: raw -> raw training from whole clean Bayer frames (uint16, or float32 DN), with the reference's
+    defaults (:55-70) and `args` keys.  Device path only (rawcrop.RawCropSource): the items are never made on the host.
+    The frame list is the reference's `infos/SID_<mode>.info` (a pickled list of dicts with 'long', 'name', 'wb', 'ccm'; looked up
+    under the working directory, or named by an `info_file` key) when it exists, else every *.npy under <root_dir>/<mode>, each
+    with an optional <stem>.json {"wb": [r, 1, b], "ccm": [...]} beside it (wb [1, 1, 1] without).  Without data, --synthetic N
+    makes N seeded uint16 frames of `H` x `W` between bl and wp.  The frames' own shape, not `H` / `W`, sizes the crops."""
+
+    def __init__(self, args, synthetic=0):
+        self.args = dict(root_dir='SID', crop_per_image=8, crop_size=512, ori=False, iso=None, dgain=None, params=None, lock_wb=False,
+                         gpu_preprocess=False, dstname='SID', mode='train', wp=16383, bl=512, command='')
+        self.args.update(args)
+        self.args.setdefault('croptype', 'random')
+        self.mode = self.args['mode']
+        self.frames, self.synthetic = None, 0
+        info = self.args.get('info_file', f"infos/SID_{self.mode}.info")
+        d = f"{self.args['root_dir']}/{self.mode}"
+        if os.path.exists(info):
+            with open(info, 'rb') as f:
+                infos = pkl.load(f)
+            log(f'>> Successfully load "{info}" (Length: {len(infos)})')
+            self.datapath, self.names = [i['long'] for i in infos], [i['name'] for i in infos]
+            self.wbs, self.ccms = [np.asarray(i['wb'], np.float64) for i in infos], [i.get('ccm') for i in infos]
+        elif _npy_files(d):
+            self.datapath = _npy_files(d)
+            self.names = [os.path.basename(p)[:-4] for p in self.datapath]
+            self.wbs, self.ccms = [], []
+            for p in self.datapath:
+                side = {}
+                if os.path.exists(p[:-4] + '.json'):
+                    import json
+                    with open(p[:-4] + '.json') as f:
+                        side = json.load(f)
+                self.wbs.append(np.asarray(side.get('wb', [1., 1., 1.]), np.float64))
+                self.ccms.append(np.asarray(side['ccm'], np.float32) if 'ccm' in side else None)
+        elif synthetic:
+            self.synthetic = int(synthetic)
+            self.datapath, self.names = [], [f'synthetic_{i:04d}' for i in range(self.synthetic)]
+            self.wbs, self.ccms = [np.ones(3)] * self.synthetic, [None] * self.synthetic
+            bl, wp = float(self.args['bl']), float(self.args['wp'])
+            base = S.synth_clean(self.args['H'], self.args['W'])
+            self.frames = [np.round(bl + (wp - bl) * np.roll(base, (37 * i, 101 * i), (0, 1)) * (0.4 + 0.6 * ((i * 7) % 10) / 9.0))
+                           .astype(np.uint16) for i in range(self.synthetic)]
+        else:
+            raise FileNotFoundError(f"no {info} and no raw frames (*.npy) under {d}; pass --synthetic N to train on synthetic frames")
+        heads = None if self.frames is None else [(f.shape, f.dtype) for f in self.frames]
+        self.H, self.W, _ = R.frame_shape(self.datapath or self.names, heads)
+        self.h, self.w = self.H // 2, self.W // 2
+        if self.mode == 'train':
+            R.check_crops(self.h, self.w, int(self.args['patch_size']), int(self.args['crop_per_image']), self.args['croptype'])
+        self.sigma = -1
+
+    def __len__(self):
+        return len(self.names)
+
+    def __getitem__(self, idx, rng=None):
+        raise NotImplementedError("SID_Raw_Dataset items are made on the GPU (rawcrop.RawCropSource), not on the host")
+
+
 def _npy_files(d):
     return sorted(str(p) for p in Path(d).glob('*.npy')) if os.path.isdir(d) else []
 
 
 def img2raw_source(ds, device):
-    """The device sRGB -> raw path (img2raw.Img2RawSource) of a dataset whose files are sRGB crops; None for packed raw or synthetic
+    """The device path of a dataset: rawcrop.RawCropSource for SID_Raw_Dataset's frames; the sRGB -> raw path
+    (img2raw.Img2RawSource) of a dataset whose files are sRGB crops; None for packed raw or synthetic
     patches.  A directory mixing both kinds raises here, before any step."""
+    if isinstance(ds, SID_Raw_Dataset):
+        return R.RawCropSource(ds.datapath or ds.names, ds.args, device, ds.wbs, ds.ccms, ds.frames)
     if not ds.datapath or I.crop_kind(ds.datapath) != 'srgb':
         return None
     if isinstance(ds, DIV2K_PG_Dataset):
@@ -297,6 +367,8 @@ class AWGN_Trainer:
         if self.mode == 'train':
             self.dst_train = globals()[self.args['dst_train']['dataset']](self.args['dst_train'], self.parser.synthetic)
             self.src_train = img2raw_source(self.dst_train, self.device)
+            # one reference "batch" of SID_Raw_Dataset is batch_size frames x crop_per_image patches (tensor_dimxto4 flattens them)
+            self.step_batch = self.hyper['batch_size'] * (self.src_train.cpi if isinstance(self.src_train, R.RawCropSource) else 1)
         self.change_eval_dst('eval')
 
     # -- trainer_base.py:48-82 ------------------------------------------------------------------------------------------------
@@ -364,7 +436,7 @@ class AWGN_Trainer:
         return imgs_lr, imgs_hr, sigma
 
     def _epoch_batches(self, epoch):
-        if self.src_train is not None:                 # sRGB crops: one img2raw launch per batch, noise slots numbered per epoch
+        if self.src_train is not None:                 # sRGB crops / raw frames: one launch per batch, noise slots numbered per epoch
             gen, key = I.train_streams(epoch, self.rank)
             for b, idx in enumerate(shard_batches(len(self.dst_train), self.hyper['batch_size'], epoch, self.rank, self.world)):
                 data = self.src_train.batch(idx, gen, key, b * len(idx))
@@ -400,7 +472,7 @@ class AWGN_Trainer:
             self.trainer.history.append((epoch, lr, losses))
             D.barrier()
             if self.rank == 0:
-                log(f'Epoch {epoch}: lr={lr:.2e}, {nb} batches of {self.hyper["batch_size"]} per rank, loss={np.mean(losses):.5f}, '
+                log(f'Epoch {epoch}: lr={lr:.2e}, {nb} batches of {self.step_batch} per rank, loss={np.mean(losses):.5f}, '
                     f'PSNR={self.train_psnr.avg:.2f}, {time.perf_counter() - t0:.2f} s', log=self.logfile)
                 if epoch % self.hyper['save_freq'] == 0:
                     sd = self.state_dict()
