@@ -174,7 +174,7 @@ typedef struct YondConvDesc {
                              tile's weights stationary in LDS and the pixels loaded straight into registers -- only for a descriptor
                              yond_gemm_k1_stationary_supported accepts, YOND_EUNSUPPORTED otherwise; 7 the 3x3 stride-2 layer of algo 3
                              (split planes in, planes of 4 out, with or without dst2; the same packed weights, the same bits) on 8-row
-                             tiles, two output rows per wave, one input image in LDS (csrc/conv_s2_tall.hip) -- only for a descriptor
+                             tiles, two output rows per wave, one or two input images in LDS (csrc/conv_s2_tall.hip) -- only for a descriptor
                              yond_conv_s2_tall_supported accepts, YOND_EUNSUPPORTED otherwise */
     /* Fused output projection (archs/Unet.py:466-470 `conv10` + residual + data_inv_normalize, i.e. what yond_conv_out_f32
        does as a kernel of its own): when out4_dst is set the convolution must produce ONE 32-channel tile (Cout = tn = 32,

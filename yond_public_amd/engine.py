@@ -63,9 +63,11 @@ K1_D2_LEVELS = (3,)                 # decoder levels whose GEMM also stores SiLU
                                     # level 3 274 -> 254-262 us, level 2 302 -> 293-303, level 1 362 -> 357-361: kept where it is clear of the noise.  () = off
 K1_STATIONARY_LEVELS = (2, 1, 0)    # decoder levels (of the GEMM's output: 2 = the GEMM 3 -> 2) whose GEMM runs with stationary weights and pixels loaded straight into
                                     # registers (descriptor algo 6, csrc/gemm_k1_stationary.hip) where the library takes the descriptor; bit-identical to the template.  () = off
-S2_TALL_LEVELS = (0, 1, 2)          # levels (of the layer's INPUT: 0 = the layer 0 -> 1) whose stride-2 layer runs on 8-row tiles, two output rows per wave, one input image in
-                                    # LDS (descriptor algo 7, csrc/conv_s2_tall.hip) where the library takes the descriptor; bit-identical to the template.  () = off
-                                    # (level 3, the layer 3 -> 4: 384 tiles of 8 rows are 1.5 rounds of 256 workgroups -- 13.5 us slower than the template at the cfg-2 shape: off; profiles/s2_tall_ab.txt)
+S2_TALL_LEVELS = (0, 1, 2, 3)       # levels (of the layer's INPUT: 0 = the layer 0 -> 1) whose stride-2 layer runs on 8-row tiles, two output rows per wave (descriptor algo 7,
+                                    # csrc/conv_s2_tall.hip: one input image in LDS at 32 input channels, two images and the weights in registers below) where the library takes the
+                                    # descriptor; bit-identical to the template.  () = off
+                                    # (level 3, the layer 3 -> 4: 384 tiles of 8 rows are 1.5 rounds of 256 workgroups -- the one-image form lost 13.5 us to the template there; the
+                                    # two-image form is 7 us ahead per launch and ahead in all three headline pairs with and without it: on; profiles/s2_two_image_ab.txt)
 K1_D2_LEVELS_HALF = ()              # ... on the fp16 path's h-only flow: none (the GEMM takes its 128-column tile instead, which has no second output)
 SP_CONV1_MIN_LEVEL = 3              # from this level down a stride-2 layer also stores SiLU(x) in split planes (YondConvDesc.dst2), so that the
                                     # next block's conv1 stages by LDS-DMA alone (there conv1 would repeat the SiLU + split per output-channel tile)
