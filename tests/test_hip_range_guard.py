@@ -2,11 +2,13 @@
 
 A kernel that stages or stores an fp32 value as fp16 halves ORs bit 0 into its status word when a value leaves fp16's range
 (|a| > 65504) or is NaN; the host then repeats the forward on the fp32-input kernels.  The raising sites, from
-`grep -n "atomicOr(.*status" yond_public_amd/csrc` (SITES below holds the same list for the CPU test that keeps it current):
+`grep -nE "atomicOr[(].*(status|YOND_STATUS_)" yond_public_amd/csrc` (SITES below holds the same list for the CPU test that keeps it current):
 
   conv_split_kernel.h  one atomicOr at the kernel's end for three accumulation sites: the staged input (NHWC / planes of 4), the
                        split-plane or h-only-plane store (PRODUCER side: the consumer reads finished halves by LDS-DMA and
                        cannot see the value), the second output SiLU(value) (dst2, producer side)
+  conv_s2_tall.hip     the stride-2 layer on 8-row tiles (descriptor algo 7), both forms: its second output SiLU(value) (dst2, producer side); the
+                       pointer is parked in a vector register under another name, the flag constant names the site
   conv.hip             the generic kernel's half-precision modes (fp16 fragments, algo 2; split operands for 1x1 layers, algo 5)
   gemm_split.hip       two words: word 0 an x operand, word 1 a weight with |w| >= 32
   wgrad_split.hip      a staged 2^11 dy part: |dy| >= 31.9
@@ -18,8 +20,13 @@ A kernel that stages or stores an fp32 value as fp16 halves ORs bit 0 into its s
 Kernel level: ONE element of a well-scaled tensor replaced, at the first pixel / first channel, the last valid pixel of a ragged
 tile / last real channel, and an interior position: 65000 leaves the word at 0 and the output within the split-operand bound
 (tests/split_model.py); 7.0e4, +inf and NaN set the bit.  False positives: ragged tiles and zero-padded channels inside a larger
-NaN-filled allocation must neither raise the flag nor touch the canary.  Network level: one layer regained by 1e6 and its
-consumer by 1e-6 at five depths of three networks on both precisions."""
+NaN-filled allocation must neither raise the flag nor touch the canary.  The 8-row stride-2 kernel's site: ONE output element at 6.0e4 / 1.0e5
+at the first pixel, the last valid pixel of the ragged tiles, lane 31 of a full tile and an interior pixel, first and last channel, beside the
+template in a second status slot; and across the tile walk of its persistent workgroups.  Network level: one layer regained by 1e6 and its
+consumer by 1e-6 at five depths of three networks on both precisions.
+Known and left as it is: in the epilogues that store halves (epilogue_sp, epilogue_direct, the 8-row kernel's) the masked lanes of a partial tile add
+the finite values they formed from real input rows to the guard's maximum, so a crafted input can raise the flag with no stored value out of range --
+the guard is conservative there, the repeated fp32 forward is still correct."""
 import os
 import re
 import warnings
@@ -35,8 +42,8 @@ gpu = pytest.mark.gpu
 DEV = 'cuda:0'
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-# file -> number of `atomicOr(<...>status...` statements the table above accounts for
-SITES = {"conv_split_kernel.h": 1, "conv.hip": 1, "gemm_split.hip": 2, "wgrad_split.hip": 1, "conv_split.hip": 2, "block0_fused.hip": 1}
+# file -> number of `atomicOr(<...>status...` / `atomicOr(<...>YOND_STATUS_...` statements the table above accounts for
+SITES = {"conv_split_kernel.h": 1, "conv_s2_tall.hip": 1, "conv.hip": 1, "gemm_split.hip": 2, "wgrad_split.hip": 1, "conv_split.hip": 2, "block0_fused.hip": 1}
 
 
 def test_every_raising_site_is_in_the_table():
@@ -47,7 +54,8 @@ def test_every_raising_site_is_in_the_table():
         if not name.endswith(('.hip', '.h')):
             continue
         with open(os.path.join(csrc, name)) as f:
-            n = len(re.findall(r"atomicOr\([^;]*status", f.read()))
+            # (one match per atomicOr whose statement names a status pointer or a status flag, whatever the pointer is called)
+            n = len(re.findall(r"atomicOr\([^;]*?(?:status|YOND_STATUS_)", f.read()))
         if n:
             found[name] = n
     assert found == SITES, found
@@ -291,12 +299,12 @@ def test_decoder_gemm_staged_and_plane_inputs(parts):
                     assert (st & 1) or not bool(torch.isfinite(got).all())
 
 
-def one_hot_layer(seed, N, C, H, W, Co, pix, big=100.0):
+def one_hot_layer(seed, N, C, H, W, Co, pix, big=100.0, co=None):
     """A tame layer whose output exceeds 65504 at exactly ONE element: input 1000 at one pixel / channel, centre-tap weight `big`."""
     g, x, w, b = tame(seed, N, C, H, W, Co)
     w = w * 0.01
     n, yy, xx = pix
-    ci, co = C - 1, Co - 1
+    ci, co = C - 1, Co - 1 if co is None else co
     x[n, yy, xx, ci] = 1000.0
     w[co, ci] = 0.0
     w[co, ci, 1, 1] = big
@@ -367,6 +375,143 @@ def test_producer_raises_for_the_second_output(parts, C, N, H, W, where):
         second = plan._new_sp('second', N, Ho, Wo, 2 * C, parts)
         plan._conv(pc, xin, None, N, H, W, gp4, algo=algo, in_fmt=1, out_fmt=2, dst2=second)
         assert (word(plan) & 1) == int(over), (big, where)
+
+
+# output pixels (n, y, x) of the 9 x 33 output of an 18 x 66 input, two images: the first; the last valid pixel of the ragged row and column
+# tiles; the second row of row group 3 at lane 31 of a full tile; an interior pixel
+TALL_PIXELS = [(0, 0, 0), (1, 8, 32), (0, 7, 31), (1, 4, 17)]
+
+
+@gpu
+@pytest.mark.parametrize("first_channel", [True, False], ids=["channel_0", "last_channel"])
+@pytest.mark.parametrize("opix", TALL_PIXELS, ids=lambda p: "n%d_y%d_x%d" % p)
+def test_s2_tall_guard_single_element(opix, first_channel):
+    """The raising site of conv_s2_tall.hip (descriptor algo 7, two-image form, 128 -> 256): tame input, exactly ONE output element at 6.0e4 (silent)
+    or at 1.0e5 (raised) -- with the second output only: planes of 4 are float32.  The template runs on the same input in a second status slot: the
+    words and both outputs are equal."""
+    from test_hip_conv import to_sp
+    from test_hip_s2_tall import bits, run_pair
+    from yond_public_amd.engine import _PackedConv
+    C, Co, N, H, W = 128, 256, 2, 18, 66
+    pix = (opix[0], 2 * opix[1], 2 * opix[2])                       # the centre tap of output (y, x) reads input (2 y, 2 x)
+    plan = status_plan()
+    for big, over in ((60.0, False), (100.0, True)):
+        x, w, b, co = one_hot_layer(C + opix[2], N, C, H, W, Co, pix, big, co=0 if first_channel else None)
+        pc = _PackedConv(plan.dev, w, b, 3, 2, [C])
+        xin = to_sp(x)
+        for d2 in (False, True):
+            out = run_pair(plan, pc, xin, N, H, W, Co, d2, 0)       # (asserts the tags: the template in slot 0, /tall in slot 1)
+            torch.cuda.synchronize()
+            st = plan.status.cpu()
+            plan.status.zero_()
+            plan.status_slot = 0
+            want = int(over and d2)
+            assert (int(st[0]), int(st[1])) == (want, want), (opix, co, big, d2, st)
+            gp4 = out[True][0]
+            assert int((gp4.abs() > 65504.0).sum()) == int(over) and float(gp4.abs().max()) > 5.9e4
+            assert torch.equal(bits(out[True][0]), bits(out[False][0]))
+            if d2:
+                assert torch.equal(bits(out[True][1]), bits(out[False][1]))
+
+
+@gpu
+@pytest.mark.parametrize("where", ['first', 'last'])
+def test_s2_tall_guard_survives_the_tile_walk(where):
+    """256 -> 512, output 40 x 224: 280 tiles on 256 persistent workgroups.  The single 1.0e5 element at the first / the last output pixel, both tile
+    orders: in one order of each the element lies in a tile whose workgroup goes on to a second tile -- the maximum lives across tiles -- and all
+    four launches raise the flag and equal the template."""
+    from test_hip_conv import to_sp
+    from test_hip_s2_tall import bits, run_pair
+    from yond_public_amd.engine import _PackedConv
+    C, Co, N, H, W = 256, 512, 1, 80, 448
+    Ho, Wo = H // 2, W // 2
+    opix = (0, 0, 0) if where == 'first' else (0, Ho - 1, Wo - 1)
+    x, w, b, co = one_hot_layer(7, N, C, H, W, Co, (0, 2 * opix[1], 2 * opix[2]), 100.0)
+    plan = status_plan()
+    pc = _PackedConv(plan.dev, w, b, 3, 2, [C])
+    xin = to_sp(x)
+    for order in (0, 1):
+        out = run_pair(plan, pc, xin, N, H, W, Co, True, order)
+        torch.cuda.synchronize()
+        st = plan.status.cpu()
+        plan.status.zero_()
+        assert (int(st[0]), int(st[1])) == (1, 1), (where, order, st)
+        assert int((out[True][0].abs() > 65504.0).sum()) == 1
+        assert torch.equal(bits(out[True][0]), bits(out[False][0])) and torch.equal(bits(out[True][1]), bits(out[False][1]))
+
+
+@gpu
+@pytest.mark.parametrize("kernel", ['stationary', 's2_tall'])
+def test_stationary_and_tall_consumers_of_a_bad_plane_value(kernel):
+    """The sibling of test_decoder_gemm_staged_and_plane_inputs for the two kernels written after the template (descriptor algo 6 and 7, no
+    second output): consumers of finished planes.  One input element of 7.0e4, inf or NaN stored into the planes: the consumer raises nothing of
+    its own (the producer of the planes has), and its output is not all finite; with 65000 it is finite and within the float64 bound."""
+    from test_hip_conv import from_p4, nchw, nhwc, sp_decode, to_sp
+    from test_hip_split_stress import check, dec_eval, dec_threshold
+    from yond_public_amd.engine import _PackedConv
+    N = 2
+    g = torch.Generator().manual_seed(37)
+    plan = status_plan()
+    if kernel == 'stationary':
+        c, h, w = 64, 9, 20
+        srcs = [torch.randn(N, h, w, 2 * c, generator=g), torch.randn(N, 2 * h, 2 * w, c, generator=g)]
+        wf = torch.randn(3 * c, c, 2, 2, generator=g) / (3 * c) ** 0.5
+        bf = torch.randn(c, generator=g)
+        pc = _PackedConv(plan.dev, wf, bf, 1, 1, [2 * c, c], shuffle=True)
+        tag = "conv_split_kernel<k1,64,2>/stationary"
+    else:
+        C, H, W = 64, 18, 40
+        srcs = [torch.randn(N, H, W, C, generator=g)]
+        wf = torch.randn(2 * C, C, 3, 3, generator=g) / (3 * C ** 0.5)
+        bf = torch.randn(2 * C, generator=g)
+        pc = _PackedConv(plan.dev, wf, bf, 3, 2, [C])
+        tag = "conv_split_kernel<2,64,2>/tall"
+
+    def launch(ts):
+        plan.prof = []
+        if kernel == 'stationary':
+            dst = torch.full((N * c * 4 * h * w,), float('nan'), device=DEV)
+            plan._conv(pc, to_sp(ts[0]), to_sp(ts[1]), N, h, w, dst, algo='split', in_fmt=1, out_fmt=2, stationary=True)
+            shape = (N, 2 * h, 2 * w, c)
+        else:
+            dst = torch.full((N * 2 * C * (H // 2) * (W // 2),), float('nan'), device=DEV)
+            plan._conv(pc, to_sp(ts[0]), None, N, H, W, dst, algo='split', in_fmt=1, out_fmt=2, s2_tall=True)
+            shape = (N, H // 2, W // 2, 2 * C)
+        tags, plan.prof = [pr[0] for pr in plan.prof], None
+        assert tags == [tag], tags
+        return word(plan), from_p4(dst, *shape)
+
+    def bound(ts):
+        """(y, T) [N][H][W][C] from the values the planes hold."""
+        dec = [nhwc(sp_decode(to_sp(t), *((N, t.shape[3]) + tuple(t.shape[1:3])))[0]) for t in ts]
+        if kernel == 'stationary':
+            z = dec_eval(dec[0], dec[1], wf.double())
+            Tz = dec_threshold(dec[0], dec[1], wf.double(), z, 2)
+            y = z + bf.double()
+            return y, Tz + 2.0 ** -24 * (z.abs() + y.abs())
+        a64 = nchw(dec[0])
+        z = F.conv2d(a64, wf.double(), stride=2, padding=1)
+        y, Ty = M.through_epilogue(M.threshold_conv(a64, wf, z, 2, 2), z, None, bf.double()[None, :, None, None])
+        return nhwc(y), nhwc(Ty)
+
+    st, got = launch(srcs)
+    assert st == 0 and bool(torch.isfinite(got).all())
+    for which, t in enumerate(srcs):
+        for pos in positions(*t.shape):
+            for bad in (65000.0,) + BAD:
+                tc = t.clone()
+                tc[pos] = bad
+                ts = [tc if i == which else s for i, s in enumerate(srcs)]
+                st, got = launch(ts)
+                if bad == 65000.0:
+                    assert st == 0 and bool(torch.isfinite(got).all()), (kernel, which, pos)
+                    y, Ty = bound(ts)
+                    check(f"guard: {kernel} consumer, 65000 in source {which} at {pos}", got, y, Ty, ch_axis=3)
+                else:
+                    nf = int((~torch.isfinite(got)).sum())
+                    print(f"[guard] {kernel} consumer of planes, {bad} in source {which} at {pos}: consumer status {st}, non-finite outputs {nf}")
+                    assert st in (0, 1), (kernel, which, pos, bad, st)
+                    assert nf > 0, (kernel, which, pos, bad)
 
 
 @gpu

@@ -493,7 +493,8 @@ __device__ __forceinline__ void s2t_body(const YondConvDesc& d) {
         }
     }
     if constexpr (D2) {
-        // (word_v: the descriptor's range-guard word; this raising site is held to the template's by tests/test_hip_s2_tall.py)
+        // (word_v: the descriptor's range-guard word; this raising site is in the table of tests/test_hip_range_guard.py and probed element by
+        // element, and across the tile walk, by its test_s2_tall_guard_* tests)
         if (word_v && !amax.at_most(65504.0f)) atomicOr(word_v, YOND_STATUS_HALF_OVERFLOW);   // an h half became +-inf
     }
     if (clk_on) {
