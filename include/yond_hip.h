@@ -244,6 +244,14 @@ int yond_conv_config(int ksize, int stride, int cin, int cout, int shuffle, int 
 int yond_pack_conv_weight_f32(const float* w, int cout, int cin, int ksize, int tn, int kc, float* dst);
 /* as yond_pack_conv_weight_f32, every weight stored as the half pair {fp16(w), fp16((w - fp16(w)) * 2^11)} (algo 5) */
 int yond_pack_conv_weight_split_f32(const float* w, int cout, int cin, int ksize, int tn, int kc, float* dst);
+/* Non-finite inputs (algo 0 and 1, the fp32-input MFMA kernels): an output is finite, and as accurate as without them, whenever its input FOOTPRINT
+ * holds no NaN or infinity -- the ksize x ksize window for algo 0; for algo 1 the 4 x 4 input tile of the output's 2 x 2 patch (rows 2i - 1 .. 2i + 2,
+ * columns 2j - 1 .. 2j + 2 for outputs (2i .. 2i + 1, 2j .. 2j + 1)) is what is promised.  (By the zeros of B^T an output of F(2x2, 3x3) reads only
+ * planes fed by its own 3 x 3 window, and the kernel was measured to confine a NaN / infinity to exactly that window; the tile is the rule that survives
+ * another transform.)  Nothing else leaks: lanes outside the image read pixel 0 of the source (element 0 of the residual) and discard it, so a NaN there
+ * stays in its own footprint (tests/test_hip_fp32_mfma.py).  Accuracy of algo 1 inside the window: every input is multiplied by sums of ALL three taps of
+ * its filter row and column (U = G g G^T) that cancel only algebraically, so an output's rounding error scales with |input| x the largest tap it meets,
+ * not with the products it keeps (tests/fp32_model.py has the per-output bound, DESIGN section 3 the measured ratio to a direct convolution). */
 int yond_conv2d_f32(const YondConvDesc* desc, void* stream);
 
 /* Winograd F(2x2,3x3) variant of the 3x3 stride-1 convolution (same descriptor, algo = 1): 16 instead of 36

@@ -39,7 +39,8 @@ def run_conv(w, b, ksize, stride, splits, xs, N, H, W, shuffle=False, **kw):
     return dst.cpu()
 
 
-@pytest.mark.parametrize("C,Co,N,H,W", [(32, 32, 1, 24, 40), (64, 64, 2, 16, 32), (32, 64, 1, 9, 33), (128, 128, 1, 8, 32)])
+@pytest.mark.parametrize("C,Co,N,H,W", [(32, 32, 1, 24, 40), (64, 64, 2, 16, 32), (32, 64, 1, 9, 33), (128, 128, 1, 8, 32),
+                                        (32, 96, 3, 100, 200)])     # 819 tiles of 8 x 32 x 32 on 512 workgroups: a second tile per workgroup
 def test_conv3x3_s1_plain(C, Co, N, H, W):
     g = torch.Generator().manual_seed(C + H)
     x = torch.randn(N, C, H, W, generator=g)
@@ -78,10 +79,12 @@ def test_conv3x3_two_source_leaky():
 @pytest.mark.parametrize("C,Co,N,H,W", [(64, 64, 1, 8, 32), (64, 64, 2, 16, 64), (32, 64, 1, 9, 33), (128, 128, 1, 24, 40),
                                         (256, 64, 1, 94, 126), (32, 32, 2, 24, 72), (64, 32, 1, 17, 40),
                                         (64, 64, 1, 1, 1), (64, 64, 1, 2, 3), (128, 64, 2, 4, 4),
-                                        (32, 32, 1, 200, 352), (64, 64, 1, 136, 288)])      # > 256 tiles: several tiles per workgroup
+                                        (32, 32, 1, 200, 352), (64, 64, 1, 136, 288),       # 13 x 11 = 143 tiles of 16 x 32 and 17 x 9 = 153 of 8 x 32: the largest
+                                                                                            # single-round launches (one tile per workgroup, 256 workgroups)
+                                        (32, 128, 3, 56, 416)])                             # 2 x 7 x 13 x 3 = 546 tiles: up to three tiles per workgroup
 def test_conv3x3_winograd_plain(C, Co, N, H, W):
     """Winograd F(2x2,3x3) kernel (algo 1) against the float64 direct convolution: same tolerance as the direct
-    kernel; partial tiles, odd extents, several tiles per workgroup."""
+    kernel; partial tiles, odd extents, several tiles per workgroup (the walk itself, element by element: tests/test_hip_fp32_mfma.py)."""
     g = torch.Generator().manual_seed(C + H)
     x = torch.randn(N, C, H, W, generator=g)
     w = torch.randn(Co, C, 3, 3, generator=g) / (3 * C ** 0.5)
