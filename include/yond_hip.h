@@ -916,6 +916,37 @@ int yond_pg_noise_hist_f32(const float* clean, int B, int H, int W, const YondPG
                            double hint_inv, unsigned long long* counts /* device */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * M4  defective pixels (bpc.hip): the reference's repair on a list of points (utils/isp_ops.py:152-160 repair_bad_pixels) and, as this
+ * project's extension, blind detection from the noise model with the repair in the same pass.  The float64 NumPy model
+ * tests/bpc_model.py is the specification.  in / out: float32 Bayer mosaics [H][W], H and W even, H * W < 2^31.
+ *     nbh(y, x)   the same-colour 3x3 neighbourhood: the nine pixels (cy(y + 2 dy), cx(x + 2 dx)), dy, dx in {-1, 0, 1}; cy clamps to
+ *                 [y & 1, H - 2 + (y & 1)], cx likewise -- cv2.medianBlur(plane, 3)'s replicated border on each plane of bayer2rggb.
+ *     m(y, x)     the median of nbh(y, x), centre included, of the INPUT frame: a selection, no rounding.
+ *   yond_bpc_repair_list_f32     out[r][c] = m(r, c) for the n points (r, c) of `points` (device int32 [n][2]); every other element of out
+ *       is left as it is: out holds a copy of in when the call is made (the reference computes the medians before it writes a point, so
+ *       neighbouring listed points do not see each other's repair).  A point outside the frame is skipped; duplicates are harmless.
+ *       out == in is accepted for n <= 1 only.  n == 0 launches nothing.
+ *   yond_bpc_detect_repair_f32   with hi / lo the maximum / minimum of the eight neighbours without the centre c:
+ *           hot   iff c > hi and (c - hi)^2 > t^2 * (beta1 * max(hi, 0) + beta2)
+ *           cold  iff c < lo and (lo - c)^2 > t^2 * (beta1 * max(lo, 0) + beta2)
+ *       evaluated in float64 from the float32 pixels, every difference, product and sum rounded on its own (no FMA), t^2 = t * t formed
+ *       on the host.  (beta1, beta2): variance = beta1 * x + beta2 in the frame's units.  out = m where flagged, else c.
+ *       counts   device uint32 [2] = {hot, cold}, 8-byte aligned, zeroed by the caller; exact.  A workgroup adds both with one 64-bit
+ *                atomic on the pair (hot is the low word).
+ *       coords   device int32 [cap][2] or null: (row, col) of flagged pixels in any order; when more than cap are flagged, cap of them.
+ *       out == in is refused: a neighbouring workgroup would read repaired values.
+ *       A tile of YOND_BPC_TILE_H x YOND_BPC_TILE_W pixels per workgroup, staged in LDS with a two-pixel halo.  16-byte global accesses
+ *       when in and out are 16-byte aligned and W % 4 == 0, 8-byte ones when they are 8-byte aligned, else 4-byte: same values.
+ * Non-finite pixels fault nothing; what they give is what v_min / v_max / the comparisons give.
+ * Refused (YOND_EINVAL, nothing launched): a null in / out / counts (points with n > 0), a misaligned pointer, H or W odd or < 2,
+ * H * W >= 2^31, n < 0, cap < 0, the aliasing named above.  YOND_EUNSUPPORTED: H > 65535 * YOND_BPC_TILE_H. */
+#define YOND_BPC_TILE_W 128
+#define YOND_BPC_TILE_H 32
+int yond_bpc_repair_list_f32(const float* in, float* out, int H, int W, const int* points /* device, [n][2] */, int n, void* stream);
+int yond_bpc_detect_repair_f32(const float* in, float* out, int H, int W, double beta1, double beta2, double t,
+                               unsigned* counts /* device, [2] */, int* coords /* device, [cap][2], or null */, int cap, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * I4  clean raw frames -> raw training pairs (rawcrop.hip; memory bound, 2 B in + 8 B out per output)
  * Replaces data_process/yond_datasets.py:153-212 (one item of SID_Raw_Dataset: DN normalisation, Bayer-pattern rotation, packing,
  * clip, square-root augmentation, crops, brightness / white-balance jitter, AWGN) for B patches of one side in one call.

@@ -138,6 +138,9 @@ class YOND_SIDD:
         if getattr(self.parser, 'noise_kld', None) is not None:
             raise SystemExit("--noise-kld belongs to the full-frame drivers (YOND_any / YOND_ELD / YOND_LRID): the residual histogram is taken over a whole "
                              "paired frame, YOND_SIDD's loop works on blocks")
+        if getattr(self.parser, 'bad_pixels', None) is not None or getattr(self.parser, 'synth_defects', None) is not None:
+            raise SystemExit("--bad-pixels / --synth-defects belong to the full-frame drivers (YOND_any / YOND_ELD / YOND_LRID): the repair works on a "
+                             "whole Bayer mosaic, YOND_SIDD's (and YOND_DND's) loop is handed packed blocks")
         self.initialization()
 
     def initialization(self):
@@ -557,6 +560,16 @@ class YONDParser:
                        "bins (default 0.1, the reference's edges).  Overrides pipeline.noise_kld_range")
         a.add_argument('--kld-bands', dest='kld_bands', type=int, default=None, metavar='N', help="--noise-kld: split the histograms into N intensity bands of "
                        "the clean frame, thresholds np.linspace(0, 1, N + 1)[1:-1] (default 0: none).  Overrides pipeline.noise_kld_bands")
+        from .bpc import bad_pixels_arg, synth_defects_arg
+        a.add_argument('--bad-pixels', dest='bad_pixels', type=bad_pixels_arg, default=None, metavar='FILE.npy|auto|auto:T', help="full-frame drivers: repair "
+                       "defective pixels before the frame is estimated and denoised -- FILE.npy: the camera's bad-point list, an int [n][2] array of "
+                       "(row, col), each replaced by the 3x3 median of its own CFA plane (the reference's repair_bad_pixels); auto: no list, a pixel that "
+                       "stands out from all eight same-colour neighbours by T standard deviations (default 6) of a blind noise estimate of the frame is "
+                       "repaired (this project's extension; one extra estimate per frame).  Overrides the runfile's pipeline.bad_pixels")
+        a.add_argument('--synth-defects', dest='synth_defects', type=synth_defects_arg, default=None, metavar='N[,LEVEL]', help="full-frame drivers, with "
+                       "--synth-noise or --camera-noise: N isolated stuck pixels are set in every noisy frame (LEVEL in the frame's units; default: the "
+                       "white level, ratio * 1.0), keyed by the item's name; the ground truth stays clean, and with --bad-pixels the log reports how many "
+                       "were found and how many detections were false")
         return a.parse_args(args)
 
 

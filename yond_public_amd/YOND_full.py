@@ -48,6 +48,16 @@ estimate, already in the units of the frame the pipeline is handed (exposure 1);
 the ratio applied as --synth-noise applies it; `cam:SPEC`: the camera model of --camera-noise.  `metrics[name]` gains kld, kld_cfa (the
 four CFA positions), kld_bands (`--kld-bands N` intensity bands of hr) and kld_floor, the model against itself under a second noise key:
 the sampling noise any value has to clear.  The noise keys are crc32(name + '/kld0') and crc32(name + '/kld1').
+
+`--bad-pixels FILE.npy | auto | auto:T` (runfile: pipeline.bad_pixels) takes hot and dead pixels out of every frame before it is estimated
+and denoised (yond_public_amd/bpc.py): FILE.npy is the camera's bad-point list, int [n][2] of (row, col), repaired as the reference's
+repair_bad_pixels does (utils/isp_ops.py:152-160: the 3x3 median of the point's own CFA plane); `auto` has no list -- one blind estimate
+of the frame (SimpleNLF, the runfile's k) gives the noise model, and a pixel that stands out from all eight same-colour neighbours by T
+standard deviations (default 6) is repaired in one pass; the pipeline then estimates again on the repaired frame.  The rule is this
+project's extension; two touching same-colour defects hide each other (a list handles clusters).  `metrics[name]['bad_pixels']` is
+{'hot', 'cold'}; the --save sidecar carries it and, in auto mode, up to 4096 coordinates.
+`--synth-defects N[,LEVEL]` (with --synth-noise / --camera-noise) sets N isolated stuck pixels in the noisy frame, keyed by
+crc32(name + '/defects'); the ground truth stays clean, and `metrics[name]['defects']` is {'n', 'found', 'false'} against that truth.
 """
 import os
 import time
@@ -58,6 +68,7 @@ import torch
 import yaml
 
 from . import archs as _archs
+from . import bpc as BP
 from . import camnoise as CN
 from . import data as _data
 from . import distributed as D
@@ -97,6 +108,7 @@ class SyntheticFrames:
 
 class YOND_Full:
     on_result = None               # callable(name, res): called with every item's result right before it is accounted, on the consumer stream
+    on_input = None                # callable(name, lr): called with every item's frame as it is handed to the pipeline (after noise, defects and repair)
 
     def __init__(self, args=None):
         self.parser = YONDParser().parse(args)
@@ -132,6 +144,16 @@ class YOND_Full:
         self.noise_kld, self.kld_range, self.kld_bands = NK.noise_kld_of(self.pipe, self.parser)
         for key in ('noise_kld', 'noise_kld_range', 'noise_kld_bands'):
             self.pipe.pop(key, None)
+        # --bad-pixels overrides the runfile's pipeline.bad_pixels: None | ('list', path) | ('auto', t)
+        self.bad_pixels = BP.bad_pixels_of(self.pipe, self.parser)
+        self.pipe.pop('bad_pixels', None)
+        self.synth_defects = getattr(self.parser, 'synth_defects', None)    # (n, level or None), or None
+        if self.synth_defects is not None and self.true_level is None:
+            raise SystemExit("--synth-defects sets stuck pixels in the noisy frame the driver makes: it needs --synth-noise or --camera-noise")
+        self.bad_points = None                                              # the list of --bad-pixels FILE.npy: (host int32 [n][2], device copy)
+        if self.bad_pixels is not None and self.bad_pixels[0] == 'list':
+            pts = BP.load_points(self.bad_pixels[1])
+            self.bad_points = (pts, torch.from_numpy(pts).to(self.device))  # uploaded once per run
         if not self.pipe.get('full_dn', False):
             raise SystemExit(f"{self.parser.runfile}: the full-frame drivers run runfiles with `full_dn: True` (YOND_SIDD.py handles the block layout)")
         self.model_name, self.method_name = self.args['model_name'], self.args['method_name']
@@ -184,6 +206,48 @@ class YOND_Full:
             return data
         K, sigma = self.synth_noise
         data['lr'] = PG.add_pg_noise(clean, K, sigma, wp - bl, key, [0], exposure=1.0 / float(data.get('ratio', 1)))
+        return data
+
+    def repair(self, data):
+        """--synth-defects, then --bad-pixels, on the item's input frame.  data['defects_truth']: the injected sites; data['bad_pixels']:
+        {'hot', 'cold'} (list mode: listed points above / below their median) and, in auto mode, 'points', 'overflow', 'model'."""
+        lr = data['lr']
+        if not isinstance(lr, torch.Tensor):
+            lr = torch.from_numpy(np.ascontiguousarray(lr, np.float32))
+        lr = lr.to(self.device, torch.float32).contiguous()
+        if self.synth_defects is not None:
+            n, level = self.synth_defects
+            if n > lr.numel() // 2000 and not getattr(self, '_defects_noted', False):
+                self._defects_noted = True
+                log(f"[rank {self.rank}] warning: --synth-defects {n} on a {lr.shape[0]} x {lr.shape[1]} frame is a density above 5e-4, far beyond a real "
+                    "sensor's: the blind noise estimates of so defective a frame may be no noise model, and the run can stop in the bias LUT "
+                    "(YOND_EINVAL), with or without --bad-pixels", self.logfile)
+            lr, data['defects_truth'] = BP.inject_defects(lr, n, zlib.crc32((str(data['name']) + '/defects').encode()), level,
+                                                          ratio=float(data.get('ratio', 1)))
+        if self.bad_pixels is not None and self.bad_pixels[0] == 'list':
+            pts, d_pts = self.bad_points
+            BP.check_points(pts, tuple(lr.shape))                # every frame's shape against the list
+            fixed = BP.repair_bad_pixels(lr, d_pts)
+            if len(pts):
+                idx = d_pts.long()
+                before, after = lr[idx[:, 0], idx[:, 1]], fixed[idx[:, 0], idx[:, 1]]
+                hot, cold = (int(v) for v in torch.stack([(before > after).sum(), (before < after).sum()]).cpu())
+            else:
+                hot = cold = 0
+            data['bad_pixels'] = {'hot': hot, 'cold': cold, 'points': pts, 'overflow': False}
+            lr = fixed
+        elif self.bad_pixels is not None:
+            t = self.bad_pixels[1]
+            beta1, beta2 = (float(v) for v in P.SimpleNLF(lr, k=self.pipe.get('k', 29), setting={'mode': 'self'}))
+            beta2 = max(beta2, 0.0) if np.isfinite(beta2) else beta2
+            if not (np.isfinite(beta1) and np.isfinite(beta2)) or beta1 < 0 or (beta1 == 0 and beta2 == 0):
+                log(f"[rank {self.rank}] warning: {data['name']}: the blind estimate beta1={beta1:g}, beta2={beta2:g} is no noise model: "
+                    "--bad-pixels auto skipped for this frame", self.logfile)
+                data['bad_pixels'] = {'hot': 0, 'cold': 0, 'points': np.zeros((0, 2), np.int32), 'overflow': False, 'model': None}
+            else:
+                lr, info = BP.detect_and_repair(lr, beta1, beta2, t, coords=BP.MAX_SAVED_POINTS)
+                data['bad_pixels'] = dict(info, model=(beta1, beta2, t))
+        data['lr'] = lr
         return data
 
     def model_kld(self, data, res, wp, bl):
@@ -350,18 +414,39 @@ class YOND_Full:
                 elif self.noise_kld is not None and not getattr(self, '_kld_noted', False):
                     self._kld_noted = True
                     log(f"[rank {self.rank}] --noise-kld: ignored for items without a reference frame (hr)", self.logfile)
+                bp = ""
+                if 'bad_pixels' in data:
+                    rep_bp = data['bad_pixels']
+                    self.metrics[data['name']]['bad_pixels'] = {'hot': rep_bp['hot'], 'cold': rep_bp['cold']}
+                    if rep_bp.get('model') is not None:
+                        self.metrics[data['name']]['bad_pixels_model'] = rep_bp['model']
+                    bp = f", bad pixels hot={rep_bp['hot']}, cold={rep_bp['cold']}"
+                    if 'defects_truth' in data:
+                        truth = {(int(r), int(c)) for r, c in data['defects_truth']}
+                        got = {(int(r), int(c)) for r, c in rep_bp['points']}
+                        self.metrics[data['name']]['defects'] = {'n': len(truth), 'found': len(truth & got), 'false': len(got - truth)}
+                        bp += f", found {len(truth & got)} / {len(truth)} injected, {len(got - truth)} false"
+                        if rep_bp['overflow']:
+                            bp += f" (of the first {len(got)} coordinates)"
+                elif 'defects_truth' in data:
+                    self.metrics[data['name']]['defects'] = {'n': len(data['defects_truth'])}
+                    bp = f", {len(data['defects_truth'])} injected defects left in"
                 ic = ""
                 if psnrs_ic:
                     ic = f", PSNR(ic)={psnrs_ic[-1]:.2f}, SSIM(ic)={ssims_ic[-1]:.4f}, gain={ic_gains[-1]:.5f}"
                     if self.illum_corr == 'cfa':
                         ic += " (" + "/".join(f"{v:.5f}" for v in ic_cfa[-1]) + ")"
                 log(f"[rank {self.rank}] {data['name']}: " + (f"PSNR={psnrs[-1]:.2f}, SSIM={ssims[-1]:.4f}" if psnrs else "denoised (no reference frame)") + ic
-                    + f", K={res['params'][-1][0]:.3f}, sigma={res['params'][-1][1]:.3f}" + true + kld, self.logfile)
+                    + f", K={res['params'][-1][0]:.3f}, sigma={res['params'][-1][1]:.3f}" + true + kld + bp, self.logfile)
 
             def deliver(k, data, res):
                 if callable(self.on_result):
                     self.on_result(data['name'], res)
                 info = {'rounds': [(float(q[0]), float(q[1])) for q in res['params']]}
+                if 'bad_pixels' in data:
+                    info['bad_pixels'] = {'hot': data['bad_pixels']['hot'], 'cold': data['bad_pixels']['cold']}
+                    if self.bad_pixels[0] == 'auto':
+                        info['bad_pixels_points'] = [[int(r), int(c)] for r, c in data['bad_pixels']['points'][:BP.MAX_SAVED_POINTS]]
                 if writer is not None and ic_sums is not None:
                     # the saved frame stays uncorrected (the correction needs the ground truth); its sidecar names the last round's gain
                     account(k, data, res)
@@ -374,6 +459,7 @@ class YOND_Full:
                 if writer is None or ic_sums is None:
                     account(k, data, res)
 
+            touch = self.bad_pixels is not None or self.synth_defects is not None
             streamed = STREAM_EVAL and getattr(self.parser, 'stream', True) and not self.parser.verbose and P.stream_applies(self.pipe, self.pipe, self.biaslut)
             if streamed:
                 # pipeline.denoise_stream: the estimator of the next frame on a side stream, the network passes of consecutive frames on two lanes -- every
@@ -384,6 +470,10 @@ class YOND_Full:
                     for k, data in loader:
                         if self.true_level is not None:
                             data = self.synthesise(data, wp, bl)
+                        if touch:
+                            data = self.repair(data)
+                        if callable(self.on_input):
+                            self.on_input(data['name'], data['lr'])
                         queue.append((k, data))
                         yield data['lr'], params_of(data)
                 t1 = time.perf_counter()
@@ -397,6 +487,10 @@ class YOND_Full:
                 for k, data in loader:
                     if self.true_level is not None:
                         data = self.synthesise(data, wp, bl)
+                    if touch:
+                        data = self.repair(data)
+                    if callable(self.on_input):
+                        self.on_input(data['name'], data['lr'])
                     torch.cuda.synchronize()
                     t1 = time.perf_counter()
                     res = self.IterDenoise(data, {'p': params_of(data), 'img_id': k})

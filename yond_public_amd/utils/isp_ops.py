@@ -1,5 +1,5 @@
 """Function seam of utils/isp_ops.py:57-71 -- Bayer <-> packed RGGB, bit-exact index permutations run
-as HIP copy kernels.  NumPy in -> NumPy out (as the reference), device tensor in -> device tensor out -- and :171-197, FastISP."""
+as HIP copy kernels.  NumPy in -> NumPy out (as the reference), device tensor in -> device tensor out -- :152-160, repair_bad_pixels, and :171-197, FastISP."""
 import numpy as np
 import torch
 
@@ -34,6 +34,18 @@ def rggb2bayers(rggbs):
     H, W, _ = rggbs.shape[-3:]
     flat = rggbs.reshape(-1, H, W, 4)
     return torch.stack([_P.rggb2bayer(r) for r in flat])
+
+
+def repair_bad_pixels(raw, bad_points, method='median'):
+    """utils/isp_ops.py:152-160: every listed (row, col) of the Bayer frame replaced by the 3x3 median of its own CFA plane, run by the
+    HIP kernel (bpc.repair_bad_pixels).  A new array / tensor is returned; the reference also writes into `raw`.  The kernel works on
+    float32: a NumPy frame is converted to float32 and the result back to its dtype.  That is exact for uint16 and float32 frames -- the
+    median is then a selection of the input's own values -- while a float64 frame gets the median of its values ROUNDED to float32."""
+    from .. import bpc as _bpc
+    if isinstance(raw, np.ndarray):
+        dev = torch.from_numpy(np.ascontiguousarray(raw, np.float32)).cuda()
+        return _bpc.repair_bad_pixels(dev, bad_points, method).cpu().numpy().astype(raw.dtype, copy=False)
+    return _bpc.repair_bad_pixels(raw, bad_points, method)
 
 
 def FastISP(img4c, wb=None, ccm=None, gamma=2.2):
