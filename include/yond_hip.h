@@ -947,6 +947,36 @@ int yond_bpc_detect_repair_f32(const float* in, float* out, int H, int W, double
                                unsigned* counts /* device, [2] */, int* coords /* device, [cap][2], or null */, int cap, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * M5  row noise / banding (rownoise.hip): the reference's row_denoise (utils/isp_algos.py:319-334) on a device frame.  The float64 NumPy
+ * model tests/rownoise_model.py is the specification.  in / out: float32 Bayer mosaics [H][W], H and W even, H * W < 2^31.  Two launches
+ * per frame, no host read between them.  With p = y & 1, j = y >> 1, n = H / 2, r = d / 2:
+ *   yond_rownoise_sums_f32    sums[y][c] = the float64 sum of in[y][x] over x % 2 == c (every float32 is exact in float64).  One wave
+ *       per row at a time, 16-byte loads when `in` is 16-byte aligned and W % 4 == 0, else one element per lane; a lane's partial sums
+ *       are combined by a fixed shuffle tree: the order of the additions depends on W and on that alignment alone, no atomics -- the
+ *       same call gives the same bits.  Any order of float64 additions is within (W / 2) * 2^-53 * sum |x| of the exact sum.
+ *   yond_rownoise_apply_f32   the sequence of means along the rows of one parity,
+ *           per = YOND_ROWNOISE_ROW     m_p[j]     = (sums[y][0] + sums[y][1]) / W        one offset per sensor row: the reference
+ *           per = YOND_ROWNOISE_PLANE   m_{p,c}[j] = sums[y][c] / (W / 2)                 one per row of a CFA plane: this project's extension
+ *       is smoothed by a 1-D bilateral filter of diameter d with a replicated border, jk = clamp(j + k, 0, n - 1), k = -r .. r:
+ *           w_k    = exp(-k^2 / (2 sigma_space^2)) * exp(-(m[jk] - m[j])^2 / (2 sigma_color^2))
+ *           offset = m[j] - sum_k w_k m[jk] / sum_k w_k, evaluated as sum_k w_k (m[j] - m[jk]) / sum_k w_k
+ *       (the same quantity; in this form equal means give exactly 0 and the rounding error scales with the differences, not with the
+ *       level), all in float64, and out[y][x] = (float)((double)in[y][x] - offset[y][x & 1]): one subtraction, one rounding.
+ *       Containment: a neighbour whose mean is not finite has weight 0; a row whose own mean is not finite has offset 0; where the
+ *       offset is 0 the pixel is copied, bit for bit.  offsets (device float64 [H][2], or null) receives every offset[y][c] once; with
+ *       YOND_ROWNOISE_ROW both columns are equal.  A wave computes its row's offsets from `sums` (one tap per lane), then streams the
+ *       row.  out may be in exactly (every element is read and written by one lane); otherwise the two frames must not overlap.
+ * Refused (YOND_EINVAL, nothing launched): a null in / out / sums, a pointer off its element size (sums, offsets: 8 bytes), H or W odd or
+ * < 2, H * W >= 2^31, d even or outside [1, YOND_ROWNOISE_MAX_D], sigma_color / sigma_space not finite or <= 0 (or so small that 2 sigma^2 is 0 in float64), an unknown per, an out that overlaps in
+ * without being in. */
+#define YOND_ROWNOISE_ROW 0
+#define YOND_ROWNOISE_PLANE 1
+#define YOND_ROWNOISE_MAX_D 63
+int yond_rownoise_sums_f32(const float* in, int H, int W, double* sums /* device, [H][2] */, void* stream);
+int yond_rownoise_apply_f32(const float* in, float* out, int H, int W, const double* sums /* device, [H][2] */, int per, int d,
+                            double sigma_color, double sigma_space, double* offsets /* device, [H][2], or null */, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * I4  clean raw frames -> raw training pairs (rawcrop.hip; memory bound, 2 B in + 8 B out per output)
  * Replaces data_process/yond_datasets.py:153-212 (one item of SID_Raw_Dataset: DN normalisation, Bayer-pattern rotation, packing,
  * clip, square-root augmentation, crops, brightness / white-balance jitter, AWGN) for B patches of one side in one call.

@@ -141,6 +141,9 @@ class YOND_SIDD:
         if getattr(self.parser, 'bad_pixels', None) is not None or getattr(self.parser, 'synth_defects', None) is not None:
             raise SystemExit("--bad-pixels / --synth-defects belong to the full-frame drivers (YOND_any / YOND_ELD / YOND_LRID): the repair works on a "
                              "whole Bayer mosaic, YOND_SIDD's (and YOND_DND's) loop is handed packed blocks")
+        if getattr(self.parser, 'row_denoise', None) is not None:
+            raise SystemExit("--row-denoise belongs to the full-frame drivers (YOND_any / YOND_ELD / YOND_LRID): the row means are taken over a whole "
+                             "Bayer mosaic, YOND_SIDD's (and YOND_DND's) loop is handed packed blocks")
         self.initialization()
 
     def initialization(self):
@@ -570,6 +573,14 @@ class YONDParser:
                        "--synth-noise or --camera-noise: N isolated stuck pixels are set in every noisy frame (LEVEL in the frame's units; default: the "
                        "white level, ratio * 1.0), keyed by the item's name; the ground truth stays clean, and with --bad-pixels the log reports how many "
                        "were found and how many detections were false")
+        from .rownoise import row_denoise_arg
+        a.add_argument('--row-denoise', dest='row_denoise', type=row_denoise_arg, nargs='?', const=row_denoise_arg('on'), default=None, metavar='SPEC',
+                       help="full-frame drivers: take row noise (banding) out of every frame before it is estimated and denoised, after --bad-pixels -- "
+                       "the reference's row_denoise: the means of the even and of the odd sensor rows are smoothed by a 1-D bilateral filter and "
+                       "mean - smoothed is subtracted from the row.  SPEC: empty or on, or sc=10,ss=auto,d=25,per=row|plane (sc: sigma_color in DN at "
+                       "capture; ss: sigma_space in rows, auto = 1 + ISO / 200; d: odd diameter up to 63; per=plane: one offset per row of a CFA "
+                       "plane, this project's extension).  It assumes smooth row means: on a scene, content leaks into the offsets.  Overrides the "
+                       "runfile's pipeline.row_denoise")
         return a.parse_args(args)
 
 

@@ -58,6 +58,15 @@ project's extension; two touching same-colour defects hide each other (a list ha
 {'hot', 'cold'}; the --save sidecar carries it and, in auto mode, up to 4096 coordinates.
 `--synth-defects N[,LEVEL]` (with --synth-noise / --camera-noise) sets N isolated stuck pixels in the noisy frame, keyed by
 crc32(name + '/defects'); the ground truth stays clean, and `metrics[name]['defects']` is {'n', 'found', 'false'} against that truth.
+
+`--row-denoise [SPEC]` (runfile: pipeline.row_denoise) takes row noise (banding) out of every frame before it is estimated and denoised
+(yond_public_amd/rownoise.py, the reference's row_denoise, utils/isp_algos.py:319-334), after the noise synthesis, --synth-defects and
+--bad-pixels: a stuck pixel at the white level shifts its row's mean, so defects go first.  SPEC is empty or `on`, or
+sc=10,ss=auto,d=25,per=row|plane: sc is sigma_color in DN at capture (the frame handed on is (DN - bl) / (wp - bl) * ratio, so the
+filter gets sc * ratio / (wp - bl)), ss=auto is 1 + ISO / 200 from the item's ISO (1600 for an item without one, said once in the log),
+per=plane removes one offset per row of a CFA plane.  `metrics[name]['row_noise']` is {'sigma', 'max'}, the RMS and the largest
+magnitude of the removed offsets in DN at capture; the --save sidecar carries the same.  The ground truth is untouched.  The method
+assumes smooth row means: on a scene, content leaks into the offsets (rownoise.py names the figures).
 """
 import os
 import time
@@ -76,6 +85,7 @@ from . import illum as IL
 from . import noisekld as NK
 from . import pgnoise as PG
 from . import pipeline as P
+from . import rownoise as RN
 from . import synthetic as S
 from .YOND_SIDD import YONDParser, load_estimators, log
 
@@ -108,7 +118,7 @@ class SyntheticFrames:
 
 class YOND_Full:
     on_result = None               # callable(name, res): called with every item's result right before it is accounted, on the consumer stream
-    on_input = None                # callable(name, lr): called with every item's frame as it is handed to the pipeline (after noise, defects and repair)
+    on_input = None                # callable(name, lr): called with every item's frame as it is handed to the pipeline (after noise, defects, repair and row denoising)
 
     def __init__(self, args=None):
         self.parser = YONDParser().parse(args)
@@ -154,6 +164,9 @@ class YOND_Full:
         if self.bad_pixels is not None and self.bad_pixels[0] == 'list':
             pts = BP.load_points(self.bad_pixels[1])
             self.bad_points = (pts, torch.from_numpy(pts).to(self.device))  # uploaded once per run
+        # --row-denoise overrides the runfile's pipeline.row_denoise: None | {'sc', 'ss', 'd', 'per'}
+        self.row_denoise = RN.row_denoise_of(self.pipe, self.parser)
+        self.pipe.pop('row_denoise', None)
         if not self.pipe.get('full_dn', False):
             raise SystemExit(f"{self.parser.runfile}: the full-frame drivers run runfiles with `full_dn: True` (YOND_SIDD.py handles the block layout)")
         self.model_name, self.method_name = self.args['model_name'], self.args['method_name']
@@ -208,9 +221,10 @@ class YOND_Full:
         data['lr'] = PG.add_pg_noise(clean, K, sigma, wp - bl, key, [0], exposure=1.0 / float(data.get('ratio', 1)))
         return data
 
-    def repair(self, data):
-        """--synth-defects, then --bad-pixels, on the item's input frame.  data['defects_truth']: the injected sites; data['bad_pixels']:
-        {'hot', 'cold'} (list mode: listed points above / below their median) and, in auto mode, 'points', 'overflow', 'model'."""
+    def repair(self, data, wp=None, bl=None):
+        """--synth-defects, then --bad-pixels, then --row-denoise, on the item's input frame.  data['defects_truth']: the injected sites;
+        data['bad_pixels']: {'hot', 'cold'} (list mode: listed points above / below their median) and, in auto mode, 'points', 'overflow',
+        'model'; data['row_noise']: {'sigma', 'max'} of the removed offsets in DN at capture."""
         lr = data['lr']
         if not isinstance(lr, torch.Tensor):
             lr = torch.from_numpy(np.ascontiguousarray(lr, np.float32))
@@ -247,6 +261,16 @@ class YOND_Full:
             else:
                 lr, info = BP.detect_and_repair(lr, beta1, beta2, t, coords=BP.MAX_SAVED_POINTS)
                 data['bad_pixels'] = dict(info, model=(beta1, beta2, t))
+        if self.row_denoise is not None:
+            spec = self.row_denoise
+            iso = data.get('ISO')
+            if iso is None and spec['ss'] == 'auto' and not getattr(self, '_iso_noted', False):
+                self._iso_noted = True
+                log(f"[rank {self.rank}] --row-denoise ss=auto: {data['name']} carries no ISO: ISO {RN.DEFAULT_ISO} assumed for such items "
+                    f"(sigma_space = {1 + RN.DEFAULT_ISO / 200:g})", self.logfile)
+            sc, ss, dn_per_unit = RN.frame_units(spec, data.get('ratio', 1), wp, bl, iso)
+            lr, offsets = RN.row_denoise(lr, sigma_color=sc, sigma_space=ss, d=spec['d'], per=spec['per'], return_offsets=True)
+            data['row_noise'] = RN.offsets_report(offsets, dn_per_unit)
         data['lr'] = lr
         return data
 
@@ -431,6 +455,11 @@ class YOND_Full:
                 elif 'defects_truth' in data:
                     self.metrics[data['name']]['defects'] = {'n': len(data['defects_truth'])}
                     bp = f", {len(data['defects_truth'])} injected defects left in"
+                if 'row_noise' in data:
+                    self.metrics[data['name']]['row_noise'] = dict(data['row_noise'])
+                    bp += f", row noise removed sigma={data['row_noise']['sigma']:.3f}, max={data['row_noise']['max']:.3f} DN"
+                    if self.camera_noise is not None and 'r' in self.camera_noise['code']:
+                        bp += f" (injected sigR={float(self.camera_noise['sigR']):g})"
                 ic = ""
                 if psnrs_ic:
                     ic = f", PSNR(ic)={psnrs_ic[-1]:.2f}, SSIM(ic)={ssims_ic[-1]:.4f}, gain={ic_gains[-1]:.5f}"
@@ -447,6 +476,8 @@ class YOND_Full:
                     info['bad_pixels'] = {'hot': data['bad_pixels']['hot'], 'cold': data['bad_pixels']['cold']}
                     if self.bad_pixels[0] == 'auto':
                         info['bad_pixels_points'] = [[int(r), int(c)] for r, c in data['bad_pixels']['points'][:BP.MAX_SAVED_POINTS]]
+                if 'row_noise' in data:
+                    info['row_noise'] = dict(data['row_noise'])
                 if writer is not None and ic_sums is not None:
                     # the saved frame stays uncorrected (the correction needs the ground truth); its sidecar names the last round's gain
                     account(k, data, res)
@@ -459,7 +490,7 @@ class YOND_Full:
                 if writer is None or ic_sums is None:
                     account(k, data, res)
 
-            touch = self.bad_pixels is not None or self.synth_defects is not None
+            touch = self.bad_pixels is not None or self.synth_defects is not None or self.row_denoise is not None
             streamed = STREAM_EVAL and getattr(self.parser, 'stream', True) and not self.parser.verbose and P.stream_applies(self.pipe, self.pipe, self.biaslut)
             if streamed:
                 # pipeline.denoise_stream: the estimator of the next frame on a side stream, the network passes of consecutive frames on two lanes -- every
@@ -471,7 +502,7 @@ class YOND_Full:
                         if self.true_level is not None:
                             data = self.synthesise(data, wp, bl)
                         if touch:
-                            data = self.repair(data)
+                            data = self.repair(data, wp, bl)
                         if callable(self.on_input):
                             self.on_input(data['name'], data['lr'])
                         queue.append((k, data))
@@ -488,7 +519,7 @@ class YOND_Full:
                     if self.true_level is not None:
                         data = self.synthesise(data, wp, bl)
                     if touch:
-                        data = self.repair(data)
+                        data = self.repair(data, wp, bl)
                     if callable(self.on_input):
                         self.on_input(data['name'], data['lr'])
                     torch.cuda.synchronize()

@@ -152,6 +152,8 @@ PROTOTYPES = {
     "yond_rawcrop_f32": [vp, sz, i32, i32, i32, f32, f32, vp, i32, i32, i32, vp, vp, vp, vp],
     "yond_bpc_repair_list_f32": [vp, vp, i32, i32, vp, i32, vp],
     "yond_bpc_detect_repair_f32": [vp, vp, i32, i32, f64, f64, f64, vp, vp, i32, vp],
+    "yond_rownoise_sums_f32": [vp, i32, i32, vp, vp],
+    "yond_rownoise_apply_f32": [vp, vp, i32, i32, vp, i32, i32, f64, f64, vp, vp],
 }
 # experiment builds only (include/yond_hip_experiments.h): bound when the loaded library has them
 EXPERIMENT_PROTOTYPES = {

@@ -1,5 +1,5 @@
 """Function seam of utils/isp_algos.py for the hot path: VST, inverse_VST, get_bias, stdfilt, varfilt,
-polyfit -- same names and argument meaning, executed by the HIP kernels (no CPU compute path).
+polyfit, row_denoise -- same names and argument meaning, executed by the HIP kernels (no CPU compute path).
 NumPy arrays are uploaded and the result comes back as NumPy (the reference's convention); device
 tensors stay on the device.  Scalars (the reference calls VST(0, ...) / VST(scale, ...)) are evaluated on
 the host in float64."""
@@ -104,3 +104,13 @@ def polyfit(x, y, ransac=False, clip=False, _full=False):
     th = torch.full((1,), float('inf'), dtype=torch.float64, device=xd.device)
     m = _P._moments(lap, xd.contiguous(), yd.contiguous(), th).cpu().numpy()
     return _P._fit_from_moments(m[0], m[1])
+
+
+def row_denoise(path, iso, data=None):
+    """utils/isp_algos.py:319-334: the row offsets that a bilateral filter (d = 25, sigmaColor = 10, sigmaSpace = 1 + iso / 200) along the
+    rows of each parity does not explain, subtracted from a Bayer frame by the HIP kernels (rownoise.row_denoise: float32 in and out, the
+    reference returns float64).  `data` is a device tensor [H][W]; with data=None `path` is a .npy file of one frame, uploaded as float32."""
+    from .. import rownoise as _rn
+    if data is None:
+        data = torch.from_numpy(np.ascontiguousarray(np.load(str(path), allow_pickle=False), np.float32)).cuda()
+    return _rn.row_denoise(data, iso)
