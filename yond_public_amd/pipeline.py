@@ -1030,7 +1030,10 @@ def _chain_denoise_frames(frames, net, arch, p, bufs, guard_slot):
     st = L.stream()
     p2d = get_p2d((1, 4, h, w), base=32)
     Hp, Wp = h + p2d[2] + p2d[3], w + p2d[0] + p2d[1]
-    x4 = torch.empty((B, Hp, Wp, 4), dtype=torch.float32, device=dev)
+    # K1 writes nothing for a FLAGGED frame (the host path takes it): its slice of the input stays zero, and below its maximum and t -- 0 and
+    # NaN when K <= 0 -- are replaced, so that the frame passes through the batched forward as finite numbers.  The range guard is one word
+    # per batch: left as they were, a flagged frame's NaNs tripped it and sent its unflagged batch mates to the host path as well.
+    x4 = torch.zeros((B, Hp, Wp, 4), dtype=torch.float32, device=dev)
     img_max = torch.empty(B, dtype=torch.float32, device=dev)
     k1 = lib.yond_pack_vst_norm_chain_f32 if CHAIN_K1 else lib.yond_pack_vst_norm_dev_f32
     with _stage("vst_pack"):
@@ -1038,7 +1041,13 @@ def _chain_denoise_frames(frames, net, arch, p, bufs, guard_slot):
             L.check(k1(L.ptr(lr), H, W, L.ptr(x4[b]), p2d[0], p2d[1], p2d[2], p2d[3], scale, L.ptr(buf.prm), L.ptr(buf.lut_ws), LUT_CAP,
                        L.ptr(img_max[b:b + 1]), st), "yond_pack_vst_norm_chain_f32")
     plan = _plan_of(net, dev)
-    t_dev = torch.cat([buf.t for buf in bufs]).contiguous() if 'guided' in arch else None
+    fl = torch.stack([buf.prm for buf in bufs])[:, PRM['flags']].to(torch.int32)
+    flagged = (fl & (PRM_NO_FLAT_AREA | PRM_LUT_CAPACITY | PRM_BAD_ESTIMATE)) != 0          # (the flags K1 and K4 skip a frame for)
+    img_max = torch.where(flagged, torch.ones_like(img_max), img_max)
+    t_dev = None
+    if 'guided' in arch:
+        t_dev = torch.cat([buf.t for buf in bufs])
+        t_dev = torch.where(flagged, torch.zeros_like(t_dev), t_dev).contiguous()
 
     def forward_and_invert():
         y4 = plan.forward_nhwc4(x4, t_dev, ub=img_max)
