@@ -567,6 +567,10 @@ int yond_conv_wgrad_ws_f32(const float* x, const float* dy, int N, int H, int W,
  * ([9][Cout][Cin]); needs |dy| < 32 (bit 0 of *status is set otherwise: TrainStep's loss scale keeps it there).
  * yond_conv_wgrad_split_ws_bytes returns 0 for a layer the kernel does not take (the caller keeps yond_conv_wgrad_ws_f32). */
 size_t yond_conv_wgrad_split_ws_bytes(int N, int H, int W, int Cin, int Cout);
+/* Read-only: the geometry yond_conv_wgrad_split_f32 would run this layer with -- out[0] the tile configuration (1..5; 0: the layer is
+ * not taken and the other four are 0), out[1] the number of K slices, out[2] the steps per slice, out[3] the X ring's pixels, out[4]
+ * the dynamic LDS bytes.  Host only, no launch (tests assert the geometry a case reaches).  YOND_EINVAL for a null out. */
+int yond_conv_wgrad_split_plan(int N, int H, int W, int Cin, int Cout, int out[5]);
 int yond_conv_wgrad_split_f32(const float* x, const float* dy, int N, int H, int W, int Cin, int Cout, float* dw,
                               int with_bias /* bit 0: dw has 9 Cout Cin + Cout floats, the last Cout = db[co] = sum_p dy[p][co];
                                                bit 1: the weight gradient in OIHW order, dw[co][ci][tap] */,

@@ -105,6 +105,7 @@ PROTOTYPES = {
     "yond_conv_wgrad_ws_f32": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp],
     "yond_conv_wgrad_ws_bytes": [i32, i32, i32, i32, i32, i32, i32, i32, i32],
     "yond_conv_wgrad_split_ws_bytes": [i32, i32, i32, i32, i32],
+    "yond_conv_wgrad_split_plan": [i32, i32, i32, i32, i32, C.POINTER(i32)],
     "yond_conv_wgrad_split_f32": [vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, sz, vp, vp],
     "yond_colsum_f32": [vp, sz, i32, vp, vp],
     "yond_film_silu_supported": [i32],

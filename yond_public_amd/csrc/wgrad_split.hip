@@ -426,6 +426,14 @@ extern "C" size_t yond_conv_wgrad_split_ws_bytes(int N, int H, int W, int Cin, i
     return p.cfg ? (size_t)p.nslices * ((size_t)9 * Cout * Cin + Cout) * sizeof(float) : 0;
 }
 
+// what wgs_plan decides for a layer, for callers that want to know which geometry a shape reaches (no launch)
+extern "C" int yond_conv_wgrad_split_plan(int N, int H, int W, int Cin, int Cout, int out[5]) {
+    if (!out) return YOND_EINVAL;
+    const WgsPlan p = wgs_plan(N, H, W, Cin, Cout);
+    out[0] = p.cfg; out[1] = p.nslices; out[2] = p.steps_per_slice; out[3] = p.ring; out[4] = (int)p.lds;
+    return YOND_OK;
+}
+
 template <int PA, int PB, int KS, int KPW>
 static int wgs_launch(const WgsGeom& g, const WgsPlan& p, hipStream_t st) {
     auto kern = wgrad_split_kernel<PA, PB, KS, KPW>;
