@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from noise_replay import gather_model as _gather_model
 from yond_public_amd import img2raw as I
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -74,23 +75,6 @@ def test_transfer_tables(g):
     lv = torch.arange(256, dtype=torch.float32) / 255.
     assert torch.equal(I.curve_host(np.uint8, 255.), _ref_curve(lv))
     assert I.curve_host(np.uint8, 255.)[0].item() == np.float32(1e-8) ** np.float32(2.2)
-
-
-def _gather_model(crop, table, rgb2cam, gain, k):
-    """The kernel's per-element map in numpy (csrc/img2raw.hip): rotated-mosaic site -> source pixel -> curve -> CCM -> mask."""
-    H, W, _ = crop.shape
-    ho, wo = (W // 2, H // 2) if k & 1 else (H // 2, W // 2)
-    c, y, x = np.meshgrid(np.arange(4), np.arange(ho), np.arange(wo), indexing="ij")
-    i, j = 2 * y + (c >> 1), 2 * x + (c & 1)
-    Y, X = [(i, j), (j, W - 1 - i), (H - 1 - i, W - 1 - j), (H - 1 - j, i)][k]
-    ch = (Y & 1) + (X & 1)
-    v = table[crop[Y, X].astype(np.int64)]                               # [4][ho][wo][3]
-    cam = np.einsum("...j,cj->...c", v, rgb2cam.astype(np.float32)).astype(np.float32)
-    gray = cam.sum(-1, dtype=np.float32) / np.float32(3)
-    mask = (np.maximum(gray - np.float32(0.9), 0) / np.float32(0.1)) ** 2
-    gc = gain[ch]
-    o = np.take_along_axis(cam, ch[..., None], -1)[..., 0] * np.maximum(mask + (1 - mask) * gc, gc)
-    return np.clip(o, 0, 1).astype(np.float32)
 
 
 def test_gather_model_matches_the_reference(g):
