@@ -302,6 +302,18 @@ int yond_conv_out_f32(const float* feat /*[N][H][W][Cin]*/, int Cin, const float
                       const float* ub /*[N] or NULL*/, int N, int H, int W, float* dst /*[N][H][W][4]*/,
                       void* stream);
 
+/* Last layer of a plain convolution stack (DnCNN, archs/comp.py:24-32): 3x3, stride 1, zero padding, Cin -> 4,
+ *   dst = x + sign * (conv3x3(feat) + bias),   sign = +1 or -1 (YOND_EINVAL otherwise); x NULL: dst = sign * (conv + bias).
+ * fp32 operands, fp32-exact products on v_mfma_f32_4x4x1_16b_f32 (no operand is rounded to half: no range precondition, no status
+ * word), fp32 accumulation: per output and tap column one chain of 3 * Cin fused multiply-adds, then the three columns, the bias
+ * and the residual added in that order.  Cin % 16 == 0, Cin <= 128 (YOND_EUNSUPPORTED otherwise).  wpk from
+ * yond_pack_conv3x3_out4_weight_f32: w OIHW [4][cin][3][3] -> dst, 36 * cin floats.
+ * Non-finite inputs: as for algo 0 above -- an output is finite whenever its own 3 x 3 x Cin footprint (and its x) is. */
+int yond_conv3x3_out4_f32(const float* feat /*[N][H][W][Cin]*/, int Cin, const float* wpk, const float* bias /*[4] or NULL*/,
+                          const float* x /*[N][H][W][4] or NULL*/, float sign, int N, int H, int W, float* dst /*[N][H][W][4]*/,
+                          void* stream);
+int yond_pack_conv3x3_out4_weight_f32(const float* w /*[4][cin][3][3]*/, int cin, float* dst /*36*cin*/);
+
 /* 2x2 max pooling, NHWC (UNetSeeInDark, archs/Unet.py:60-72). */
 int yond_maxpool2_f32(const float* src, int N, int H, int W, int C, float* dst, void* stream);
 

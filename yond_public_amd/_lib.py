@@ -71,6 +71,8 @@ PROTOTYPES = {
     "yond_conv_in_f32": [vp, vp, i32, i32, i32, i32, vp, vp, f32, vp, i32, vp],
     "yond_pack_conv_in_weight_f32": [vp, i32, vp],
     "yond_conv_out_f32": [vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp],
+    "yond_conv3x3_out4_f32": [vp, i32, vp, vp, vp, f32, i32, i32, i32, vp, vp],
+    "yond_pack_conv3x3_out4_weight_f32": [vp, i32, vp],
     "yond_maxpool2_f32": [vp, i32, i32, i32, i32, vp, vp],
     "yond_film_f32": [vp, i32, vp, vp, i32, vp],
     "yond_box_stats_self1_f32": [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp],

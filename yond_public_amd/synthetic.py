@@ -31,10 +31,23 @@ def procedural_state_dict(net, seed=0, gain=1.0):
     """Deterministic weights for a yond_public_amd.archs module: per-key seeded generator,
     fan-in-scaled normal weights, small biases, FiLM scales around 1."""
     sd = {}
-    for key, ref in sorted(net.state_dict().items()):
+    full = net.state_dict()
+    for key, ref in sorted(full.items()):
         shape = tuple(ref.shape)
         g = torch.Generator().manual_seed((seed * 1000003 + zlib.crc32(key.encode())) % (2 ** 31))
-        if key.endswith('.weight'):
+        stem = key.rsplit('.', 1)[0]
+        if stem + '.running_var' in full:
+            # a BatchNorm layer (DnCNN): non-trivial statistics, so that a wrong fold shows -- gamma in [0.5, 1.5], beta and the
+            # running mean ~ N(0, 0.1), the running variance log-uniform in [0.25, 4]
+            if key.endswith('.weight'):
+                sd[key] = 0.5 + torch.rand(shape, generator=g)
+            elif key.endswith('.running_var'):
+                sd[key] = torch.exp(math.log(0.25) + torch.rand(shape, generator=g) * math.log(16.0))
+            elif key.endswith('.num_batches_tracked'):
+                sd[key] = torch.zeros(shape, dtype=ref.dtype)
+            else:
+                sd[key] = torch.randn(shape, generator=g) * 0.1
+        elif key.endswith('.weight'):
             fan_in = shape[0] if 'upv' in key else shape[1] * shape[2] * shape[3]
             std = gain * math.sqrt(1.0 / fan_in)
             if '.gamma.0' in key or '.sfm1.0' in key or '.sfm2.0' in key:
@@ -78,6 +91,29 @@ def denoising_state_dict(net, seed=0, eps=0.004):
         for c in range(4):
             w[c, c, 0, 0] = 1.0
             w[c, 4 + c, 0, 0] = -1.0
+
+    if name == 'DnCNN':
+        # out = eps-sized perturbation + (input - box mean): the residual `x - out` returns the box mean.  Features 0-3 carry the box
+        # mean, 4-7 the input (non-negative behind the VST, so the ReLUs pass them); BatchNorm layers are the identity.
+        keys = sorted((k for k in sd if k.endswith('.weight') and sd[k].dim() == 4), key=lambda k: int(k.split('.')[1]))
+        first_layer(keys[0][:-len('.weight')])
+        for k in keys[1:-1]:
+            w = sd[k]
+            w *= eps
+            for c in range(8):
+                w[c, :8] = 0
+                w[c, c, 1, 1] = 1.0
+        for k in sd:
+            stem = k.rsplit('.', 1)[0]
+            if stem + '.running_var' in sd and not k.endswith('.num_batches_tracked'):
+                sd[k] = torch.ones_like(sd[k]) if k.endswith(('.weight', '.running_var')) else torch.zeros_like(sd[k])
+        w = sd[keys[-1]]
+        w *= eps
+        for c in range(4):
+            w[c, :8] = 0
+            w[c, 4 + c, 1, 1] = 1.0
+            w[c, c, 1, 1] = -1.0
+        return sd
 
     if name == 'UNetSeeInDark':
         first_layer('conv1_1')
