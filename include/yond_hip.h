@@ -314,6 +314,49 @@ int yond_conv3x3_out4_f32(const float* feat /*[N][H][W][Cin]*/, int Cin, const f
                           void* stream);
 int yond_pack_conv3x3_out4_weight_f32(const float* w /*[4][cin][3][3]*/, int cin, float* dst /*36*cin*/);
 
+/* ------------------------------------------------------------------------------------------------
+ * FBI_Net (archs/comp.py:264-648, case 'FBI_Net'): a blind-spot denoiser on the one-channel Bayer mosaic (csrc/fbinet.hip).
+ * Activations are [N][H][W][nf] float32 at mosaic resolution (H = 2 h, W = 2 w of the packed frame), nf = 32 or 64.  Every product
+ * is an exact fp32 product (the fp32-input MFMA, fmaf in the two edge kernels) with fp32 accumulation: no operand is rounded to half,
+ * there is no range precondition and no status word.  Every entry returns YOND_EINVAL on a NULL pointer it needs and on shapes it
+ * does not take, allocates nothing and runs on `stream`.  PReLU(x; s) = x > 0 ? x : s x, one slope per channel.
+ *
+ * yond_fbi_first_f32: n = PReLU(conv3x3 WITHOUT its centre tap (mosaic of x4, zero pad 1) + bias; slope[0]), 1 -> nf.  The mosaic
+ *   pixel (y, x) is x4[y/2][x/2][2 (y&1) + (x&1)].  wpk from yond_pack_fbi_first_weight_f32 (w [nf][1][3][3] -> 8 * nf floats).
+ * yond_fbi_tapconv_f32: n_out = PReLU(sum over the live taps t of W_t n_in(. + d_t) + bias; s1),  o_out = PReLU((n_out + o_in) / 2; s2),
+ *   nf -> nf, zero border.  set 0: the 9 taps (0,1) (0,3) (1,0) (1,4) (2,2) (3,0) (3,4) (4,1) (4,3) of a 5x5 kernel, pad 2;
+ *   set 1: centre and corners of a 3x3 kernel at dilation 3, pad 3.  wpk from yond_pack_fbi_tap_weight_f32 (w OIHW, unmasked:
+ *   [nf][nf][5][5] or [nf][nf][3][3] -> yond_fbi_taps(set) * nf * nf floats: the dead taps are not read).  n_out and o_out must not
+ *   be n_in.  yond_fbi_tile gives the pixel tile of a workgroup (tests place pixels on its seams).
+ * yond_fbi_rm_f32: o = PReLU((v + W2 PReLU(W1 v + b1; a1) + b2) / 2; a2) on npix pixels, W1, W2 [nf][nf] packed by
+ *   yond_pack_fbi_rm_weight_f32 (nf * nf floats each).  pre_slope != NULL: v is PReLU(v / pre_div; pre_slope) first (pre_div >= 1).
+ *   o_out may be NULL when sum_mode != 0.  sum_mode 0: sum is not touched, 1: sum = o, 2: sum += o.  o_out must not be v.
+ * yond_fbi_out_f32: y = W f + b, W [oc][nf], oc = 1 or 2; use_sigmoid: y0 = sigmoid_value * sigmoid(y0);
+ *   oc 2: dst4 = y0 * x4 + y1 at the same packed position, oc 1: dst4 = y0. */
+int yond_fbi_taps(int set);
+int yond_fbi_tile(int* th, int* tw);
+int yond_pack_fbi_first_weight_f32(const float* w, int nf, float* dst);
+int yond_pack_fbi_tap_weight_f32(const float* w, int nf, int set, float* dst);
+int yond_pack_fbi_rm_weight_f32(const float* w, int nf, float* dst);
+int yond_fbi_first_f32(const float* x4 /*[N][h][w][4]*/, int N, int h, int w, int nf, const float* wpk, const float* bias /*[nf]*/,
+                       const float* slope /*[1]*/, float* dst /*[N][2h][2w][nf]*/, void* stream);
+int yond_fbi_tapconv_f32(const float* n_in, const float* o_in, int set, int nf, const float* wpk, const float* bias, const float* s1,
+                         const float* s2, int N, int H, int W, float* n_out, float* o_out, void* stream);
+int yond_fbi_rm_f32(const float* v, int nf, const float* w1p, const float* b1, const float* a1, const float* w2p, const float* b2,
+                    const float* a2, const float* pre_slope /* or NULL */, int pre_div, size_t npix, float* o_out, float* sum, int sum_mode,
+                    void* stream);
+int yond_fbi_out_f32(const float* f /*[N][2h][2w][nf]*/, int nf, const float* w, const float* b, int oc, int use_sigmoid,
+                     float sigmoid_value, const float* x4 /*[N][h][w][4]; oc 2 only*/, int N, int h, int w_, float* dst4 /*[N][h][w][4]*/,
+                     void* stream);
+
+/* Minimum and maximum of the bias-corrected stabilised value that yond_pack_vst_norm_f32 / _biaslut_f32 / _batch_f32 normalise
+ * (the same device function, float64), over each of B Bayer frames [B][H][W] that share the constants and the LUT:
+ * out [B][2] float64 = (min, max) -- the reference's `lower, upper = raw_vst.min(), raw_vst.max()` of its 'fbi' branch
+ * (YOND_SIDD.py:266-267).  lut_n 0: no bias; biaslut 0: the 1-D knots (lut_y float32), else the merged row of the 2-D table
+ * (lut_y float64).  The reduction is on ordered integers: the result does not depend on the launch geometry. */
+int yond_vst_minmax_f32(const float* bayer, int B, int H, int W, double scale, double gain, double sigma, const double* lut_x,
+                        const void* lut_y, int lut_n, int biaslut, double* out /*[B][2]*/, void* stream);
+
 /* 2x2 max pooling, NHWC (UNetSeeInDark, archs/Unet.py:60-72). */
 int yond_maxpool2_f32(const float* src, int N, int H, int W, int C, float* dst, void* stream);
 

@@ -210,7 +210,7 @@ class YOND_SIDD:
 
     def VST_Denoiser(self, lr_raw, hr_raw=None, bias_corr='pre', bias_func=None, denoiser='gru32n', p=None):
         return P.VST_Denoiser(lr_raw, p, self.net, self.arch, bias_corr, bias_func, self.pipe.get('vst_type', 'exact'),
-                              device=self.device, biaslut=self.biaslut)
+                              device=self.device, biaslut=self.biaslut, denoiser=denoiser if denoiser in ('fbi', 'bm3d') else None)
 
     def _est(self, data, params):
         """What IterDenoise's estimate may read: the dataset tree and image (file estimates), the est_* sections and their networks."""

@@ -73,6 +73,16 @@ PROTOTYPES = {
     "yond_conv_out_f32": [vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp],
     "yond_conv3x3_out4_f32": [vp, i32, vp, vp, vp, f32, i32, i32, i32, vp, vp],
     "yond_pack_conv3x3_out4_weight_f32": [vp, i32, vp],
+    "yond_fbi_taps": [i32],
+    "yond_fbi_tile": [C.POINTER(i32), C.POINTER(i32)],
+    "yond_pack_fbi_first_weight_f32": [vp, i32, vp],
+    "yond_pack_fbi_tap_weight_f32": [vp, i32, i32, vp],
+    "yond_pack_fbi_rm_weight_f32": [vp, i32, vp],
+    "yond_fbi_first_f32": [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp],
+    "yond_fbi_tapconv_f32": [vp, vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp],
+    "yond_fbi_rm_f32": [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, sz, vp, vp, i32, vp],
+    "yond_fbi_out_f32": [vp, i32, vp, vp, i32, i32, f32, vp, i32, i32, i32, vp, vp],
+    "yond_vst_minmax_f32": [vp, i32, i32, i32, f64, f64, f64, vp, vp, i32, i32, vp, vp],
     "yond_maxpool2_f32": [vp, i32, i32, i32, i32, vp, vp],
     "yond_film_f32": [vp, i32, vp, vp, i32, vp],
     "yond_box_stats_self1_f32": [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp],

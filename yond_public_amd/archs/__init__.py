@@ -1,9 +1,10 @@
 """`from yond_public_amd.archs import *` mirrors `from archs import *` (YOND_SIDD.py:7) for the
-hot-path denoisers, the comparison denoiser DnCNN (archs/comp.py) and the estimation network of the `est_*` sections; classes are resolved by name from the runfile's arch['name']."""
+hot-path denoisers, the comparison denoisers DnCNN and FBI_Net (archs/comp.py) and the estimation network of the `est_*` sections; classes are resolved by name from the runfile's arch['name']."""
 import torch.nn as nn
 
 from .dncnn import DnCNN
 from .est import EstUnet
+from .fbinet import FBI_Net
 from .unet import GuidedResUnet, SNRnet, UNetSeeInDark
 
 
@@ -18,4 +19,4 @@ def initialize_weights(net):
             m.weight.data.normal_(0.0, 0.02)
 
 
-__all__ = ["GuidedResUnet", "SNRnet", "UNetSeeInDark", "DnCNN", "EstUnet", "initialize_weights"]
+__all__ = ["GuidedResUnet", "SNRnet", "UNetSeeInDark", "DnCNN", "FBI_Net", "EstUnet", "initialize_weights"]

@@ -68,6 +68,19 @@ __device__ __forceinline__ double sqrt_newton(double a) {
     return fma(e, r, s0);
 }
 
+// The bias-corrected stabilised value K1 normalises (YOND_SIDD.py:251-262), in float64: shared by pack_vst_norm_kernel and
+// vst_minmax_kernel, so that the extremes the one reports are the extremes the other sees, bit for bit.
+__device__ __forceinline__ double vst_biased(const LutLds& L, float q, float scale_f, double gain, double sigma, double c0, double s2,
+                                             double two_over_gain, int lut_n, int lut_flags) {
+    const float x32 = q * scale_f;                                  // float32 * python float -> float32
+    double fz = gain * (double)x32 + c0 + s2;                       // gain*x + (3/8)gain^2 + sigma^2 (- gain*0)
+    fz = fz > 0.0 ? fz : 0.0;
+    double v = two_over_gain * sqrt_newton(fz);
+    if (lut_n > 0) v -= (lut_flags & LUT_BIASLUT) ? biaslut_eval(L, lut_n, fmaxf(x32, 0.0f), gain, sigma)
+                                                  : lut_eval(L, lut_n, fmaxf(x32, 0.0f));
+    return v;
+}
+
 __global__ __launch_bounds__(256) void pack_vst_norm_kernel(const float* __restrict__ bayer, int H, int W,
                                                             float* __restrict__ out, int pad_l, int pad_t, int Hp,
                                                             int Wp, int mode, float scale_f, double gain, double sigma,
@@ -138,12 +151,7 @@ __global__ __launch_bounds__(256) void pack_vst_norm_kernel(const float* __restr
             if (mode == 0) {
                 u = q[c];
             } else {
-                const float x32 = q[c] * scale_f;                       // float32 * python float -> float32
-                double fz = gain * (double)x32 + c0 + s2;               // gain*x + (3/8)gain^2 + sigma^2 (- gain*0)
-                fz = fz > 0.0 ? fz : 0.0;
-                double v = two_over_gain * sqrt_newton(fz);
-                if (lut_n > 0) v -= (lut_flags & LUT_BIASLUT) ? biaslut_eval(L, lut_n, fmaxf(x32, 0.0f), gain, sigma)
-                                                              : lut_eval(L, lut_n, fmaxf(x32, 0.0f));
+                const double v = vst_biased(L, q[c], scale_f, gain, sigma, c0, s2, two_over_gain, lut_n, lut_flags);
                 u = (float)((v - lo) * inv_span);                       // (v - lo) / (hi - lo) to one float64 ulp, then ONE rounding
             }
             u = fminf(fmaxf(u, 0.0f), 1.0f);
@@ -300,6 +308,102 @@ static int launch_pack_vst(const float* bayer, int H, int W, float* out, int pad
     hipLaunchKernelGGL(pack_vst_norm_kernel, dim3((unsigned)nb), dim3(256), (size_t)use_lut * LUT_BYTES_PER_KNOT, st, bayer, H, W, out,
                        pad_l, pad_t, Hp, Wp, mode, (float)scale, gain, sigma, lo, hi, lut_x, lut_y, use_lut, lut_flags, (unsigned int*)img_max,
                        (const double*)nullptr, (const void*)nullptr, 0, B);
+    YOND_LAUNCH_CHECK();
+    return YOND_OK;
+}
+
+// ---- minimum and maximum of the value K1 normalises (the reference's `fbi` / `bm3d` branch: lower, upper = raw_vst.min(), raw_vst.max(),
+// YOND_SIDD.py:266-267).  One pass over B Bayer frames [B][H][W] that share the constants and the LUT; out [B][2] float64 = (min, max).
+// Doubles are reduced as ORDERED 64-bit integers (sign bit flipped for non-negative values, all bits for negative ones: the unsigned
+// order is the numeric one) with vector atomics: the result does not depend on the order of arrival.
+__device__ __forceinline__ unsigned long long f64_key(double v) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double f64_unkey(unsigned long long k) {
+    return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
+}
+
+__global__ void vst_minmax_init_kernel(unsigned long long* __restrict__ keys, int B) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < 2 * B) keys[i] = (i & 1) ? 0ull : ~0ull;               // (min, max)
+}
+
+__global__ void vst_minmax_decode_kernel(unsigned long long* __restrict__ keys, int B) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < 2 * B) ((double*)keys)[i] = f64_unkey(keys[i]);
+}
+
+__global__ __launch_bounds__(256) void vst_minmax_kernel(const float* __restrict__ bayer, int H, int W, float scale_f, double gain,
+                                                         double sigma, const double* __restrict__ lut_x, const void* __restrict__ lut_y,
+                                                         int lut_n, int lut_flags, unsigned long long* __restrict__ keys, int B) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lut_raw[];
+    __shared__ LutLds L;
+    __shared__ double s_lo[4], s_hi[4];
+    if (threadIdx.x == 0) {
+        L.ab = (double2*)lut_raw;
+        L.x = (double*)(L.ab + lut_n);
+    }
+    __syncthreads();
+    if (lut_n > 0) lut_prepare(L, lut_x, lut_y, lut_n, lut_flags);
+    const double c0 = 0.375 * gain * gain, s2 = sigma * sigma, two_over_gain = 2.0 / gain;
+    const int rows_all = B * H, per = (rows_all + (int)gridDim.x - 1) / (int)gridDim.x;
+    const int row_lo = blockIdx.x * per, row_hi = row_lo + per < rows_all ? row_lo + per : rows_all;
+    double vlo = INFINITY, vhi = -INFINITY;
+    int cur_b = -1;
+    auto flush = [&](int b) {
+        if (b < 0) return;
+        double lo = vlo, hi = vhi;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { lo = fmin(lo, __shfl_xor(lo, o)); hi = fmax(hi, __shfl_xor(hi, o)); }
+        __syncthreads();
+        if ((threadIdx.x & 63) == 0) { s_lo[threadIdx.x >> 6] = lo; s_hi[threadIdx.x >> 6] = hi; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            lo = fmin(fmin(s_lo[0], s_lo[1]), fmin(s_lo[2], s_lo[3]));
+            hi = fmax(fmax(s_hi[0], s_hi[1]), fmax(s_hi[2], s_hi[3]));
+            if (lo <= hi) {                                         // (a range without an element leaves +inf / -inf: nothing to report)
+                atomicMin(keys + 2 * b, f64_key(lo));
+                atomicMax(keys + 2 * b + 1, f64_key(hi));
+            }
+        }
+    };
+    for (int row = row_lo; row < row_hi; ++row) {                   // (uniform per workgroup)
+        const int bi = row / H;
+        if (bi != cur_b) { flush(cur_b); vlo = INFINITY; vhi = -INFINITY; cur_b = bi; }
+        const float* src = bayer + (size_t)row * W;
+        for (int x = threadIdx.x; x < W; x += 256) {
+            const double v = vst_biased(L, src[x], scale_f, gain, sigma, c0, s2, two_over_gain, lut_n, lut_flags);
+            vlo = fmin(vlo, v);
+            vhi = fmax(vhi, v);
+        }
+    }
+    flush(cur_b);
+}
+
+// lut_n == 0: no bias; biaslut == 0: the 1-D knots (lut_y float32); biaslut != 0: the merged row of the 2-D table (lut_y float64).
+extern "C" int yond_vst_minmax_f32(const float* bayer, int B, int H, int W, double scale, double gain, double sigma, const double* lut_x,
+                                   const void* lut_y, int lut_n, int biaslut, double* out, void* stream) {
+    if (!bayer || !out || B < 1 || H < 2 || W < 2 || (H & 1) || (W & 1) || (long long)B * H > 0x7fffffffLL) return YOND_EINVAL;
+    if (lut_n < 0 || lut_n > LUT_MAX || lut_n == 1 || (lut_n > 0 && (!lut_x || !lut_y)) || (biaslut && lut_n < 2)) return YOND_EINVAL;
+    if (!(gain > 0.0)) return YOND_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    static bool attr = false;
+    if (!attr) {
+        hipError_t e = hipFuncSetAttribute((const void*)vst_minmax_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LUT_MAX * LUT_BYTES_PER_KNOT);
+        if (e != hipSuccess) return (int)e;
+        attr = true;
+    }
+    unsigned long long* keys = (unsigned long long*)out;
+    const unsigned nk = (unsigned)((2 * (size_t)B + 255) / 256);
+    hipLaunchKernelGGL(vst_minmax_init_kernel, dim3(nk), dim3(256), 0, st, keys, B);
+    YOND_LAUNCH_CHECK();
+    size_t nb = (size_t)B * H;
+    if (nb > 1536) nb = 1536;                       // every workgroup prepares the LUT once: keep them few and long-lived
+    hipLaunchKernelGGL(vst_minmax_kernel, dim3((unsigned)nb), dim3(256), (size_t)lut_n * LUT_BYTES_PER_KNOT, st, bayer, H, W, (float)scale,
+                       gain, sigma, lut_x, lut_y, lut_n, biaslut ? (LUT_Y64 | LUT_BIASLUT) : 0, keys, B);
+    YOND_LAUNCH_CHECK();
+    hipLaunchKernelGGL(vst_minmax_decode_kernel, dim3(nk), dim3(256), 0, st, keys, B);
     YOND_LAUNCH_CHECK();
     return YOND_OK;
 }

@@ -746,6 +746,13 @@ def SimpleNLF(lr_raw, hr_raw=None, k=29, setting=None, full=False, device=None, 
 # ------------------------------------------------------------------------------------------------
 # VST -> denoiser -> inverse VST  (YOND_SIDD.py:238-299)
 # ------------------------------------------------------------------------------------------------
+def denoiser_of(pipe):
+    """The runfile's pipeline['denoiser_type'] as YOND_SIDD.py:266-279 branches on it: 'fbi' or 'bm3d'; None for every other value
+    (the network denoisers' branch: the shipped runfiles name 'gru32n' and the like)."""
+    d = (pipe or {}).get('denoiser_type')
+    return d if d in ('fbi', 'bm3d') else None
+
+
 def _plan_of(net, device):
     mod = net.module if hasattr(net, 'module') else net           # nn.DataParallel wrapper
     if not hasattr(mod, '_get_plan'):
@@ -793,8 +800,11 @@ class _Guard:
 
 
 def VST_Denoiser(lr_raw, p, net, arch, bias_corr='pre', bias_func=None, vst_type='exact', clip01=False, device=None,
-                 lr_max=None, guard=True, guard_slot=0, biaslut=None):
-    """YOND_SIDD.py:250-299 for the network denoisers.  lr_raw: Bayer [H][W] -- or a stack [B][H][W] of equally
+                 lr_max=None, guard=True, guard_slot=0, biaslut=None, denoiser=None):
+    """YOND_SIDD.py:250-299 for the network denoisers and, with denoiser == 'fbi' (the runfile's pipeline['denoiser_type']), for the
+    blind-spot denoiser archs.FBI_Net (:266-279): the bias-corrected stabilised frame is normalised by its OWN minimum and maximum
+    (yond_vst_minmax_f32, read back: one sync per frame, as the frame maximum's), per frame of a stack, not padded, and handed to the
+    network as packed Bayer; t is unused.  'bm3d' (a third-party CPU package) is not built and raises.  lr_raw: Bayer [H][W] -- or a stack [B][H][W] of equally
     sized frames that go through ONE batched forward instead of B batch-1 calls: the 32 blocks of a SIDD image, which
     share (gain, sigma) and the bias LUT (:392-407), or B independent frames (BASELINE cfg 4), for which `p`,
     `bias_func` and `lr_max` are lists with one entry per frame.  p: dict with scale, gain, sigma; returns the
@@ -802,6 +812,16 @@ def VST_Denoiser(lr_raw, p, net, arch, bias_corr='pre', bias_func=None, vst_type
     frame) spares the device reduction + sync when the caller already has it.  guard: True -- wait for the forward and
     recompute it on the fp32-input MFMA kernels if an activation left fp16's range (see _Guard); 'defer' -- return
     (result, guard) and let the caller call guard.finish() later; False -- no check."""
+    if denoiser == 'bm3d':
+        raise NotImplementedError("denoiser_type 'bm3d' is not built (the reference calls the third-party CPU package bm3d, YOND_SIDD.py:270-272)")
+    fbi = denoiser == 'fbi'
+    mod = net.module if hasattr(net, 'module') else net
+    if fbi and type(mod).__name__ != 'FBI_Net':
+        raise L.YondHipError(f"denoiser_type 'fbi' needs the network archs.FBI_Net (min/max normalisation, one-channel mosaic, no padding), "
+                             f"got {type(mod).__name__}")
+    if not fbi and type(mod).__name__ == 'FBI_Net':
+        raise L.YondHipError("the network FBI_Net runs behind the reference's 'fbi' branch only: set pipeline['denoiser_type'] to 'fbi' "
+                             f"(got denoiser={denoiser!r}; VST(0) / VST(scale) normalisation and reflect padding are the other networks')")
     lib = L.load()
     lr = _dev(lr_raw, device)
     single = lr.dim() == 2
@@ -829,16 +849,30 @@ def VST_Denoiser(lr_raw, p, net, arch, bias_corr='pre', bias_func=None, vst_type
                 mxv = maxes[i] if maxes[i] is not None else _frame_max(lr[i]).item()
                 mx = np.float32(mxv) * np.float32(ps[i]['scale'])    # lr_rggb.max() of the float32 product (:256)
                 funcs[i] = get_bias(mx, np.float64(ps[i]['sigma']), np.float64(ps[i]['gain']), device=lr.device)
-    p2d = get_p2d((1, 4, h, w), base=32)
+    p2d = (0, 0, 0, 0) if fbi else get_p2d((1, 4, h, w), base=32)
     Hp, Wp = h + p2d[2] + p2d[3], w + p2d[0] + p2d[1]
     x4 = torch.empty((B, Hp, Wp, 4), dtype=torch.float32, device=lr.device)
     img_max = torch.empty(B, dtype=torch.float32, device=lr.device)
     st = L.stream()
     consts, t_host = [], []
     # a stack whose frames share p and the LUT (the 32 blocks of a SIDD image): K1 and K4 as ONE launch each
-    shared = B > 1 and not per_frame and all(f is funcs[0] for f in funcs)
-    if shared and not lr.is_contiguous():
+    shared = B > 1 and not per_frame and all(f is funcs[0] for f in funcs) and not fbi     # ('fbi': every frame has its own lower / upper)
+    if (shared or fbi) and not lr.is_contiguous():
         lr = lr.contiguous()
+    bounds = None
+    if fbi:                                                           # :266-267, per frame (the reference runs block by block)
+        mm = torch.empty((B, 2), dtype=torch.float64, device=lr.device)
+        with _stage("vst_minmax"):
+            for i in range(B):
+                f = funcs[i]
+                lut_n = len(f) if bias_corr is not None else 0
+                L.check(lib.yond_vst_minmax_f32(L.ptr(lr[i]), 1, H, W, float(ps[i]['scale']), float(ps[i]['gain']), float(ps[i]['sigma']),
+                                                L.ptr(f.x) if lut_n else None, L.ptr(f.y) if lut_n else None, lut_n,
+                                                int(bool(lut_n) and isinstance(f, DeviceBiasRow)), L.ptr(mm[i]), st), "yond_vst_minmax_f32")
+            bounds = mm.cpu().numpy()                                 # (the one sync of this branch)
+        for i in range(B):
+            if not bounds[i, 1] > bounds[i, 0]:
+                raise L.YondHipError(f"denoiser 'fbi': frame {i} is constant behind the VST (min == max == {bounds[i, 0]}): nothing to normalise by")
     with _stage("vst_pack"):
         if shared:
             scale, gain, sigma = float(ps[0]['scale']), np.float64(ps[0]['gain']), np.float64(ps[0]['sigma'])
@@ -854,6 +888,8 @@ def VST_Denoiser(lr_raw, p, net, arch, bias_corr='pre', bias_func=None, vst_type
         for i in range(0 if shared else B):
             scale, gain, sigma = float(ps[i]['scale']), np.float64(ps[i]['gain']), np.float64(ps[i]['sigma'])
             lower, upper = vst_scalar(0, sigma, gain), vst_scalar(scale, sigma, gain)
+            if fbi:
+                lower, upper = np.float64(bounds[i, 0]), np.float64(bounds[i, 1])
             consts.append((scale, gain, sigma, lower, upper))
             t_host.append(float(np.float32(1 / (upper - lower) * (1.03 if bias_corr == 'pre' else 1.00))))   # :284-285
             f = funcs[i]
@@ -869,7 +905,7 @@ def VST_Denoiser(lr_raw, p, net, arch, bias_corr='pre', bias_func=None, vst_type
                                                L.ptr(img_max[i:i + 1]), st), "yond_pack_vst_norm_f32")
     plan = _plan_of(net, lr.device)
     t_dev = None
-    if 'guided' in arch:
+    if 'guided' in arch and not fbi:
         t_dev = torch.tensor(t_host, dtype=torch.float32).to(lr.device, non_blocking=True) if per_frame else \
             torch.full((B,), t_host[0], dtype=torch.float32, device=lr.device)
     exact_inverse = bias_corr is None and vst_type == 'exact'
@@ -941,7 +977,8 @@ def chain_applies(lr, net, arch, pipe, biaslut=None):
     return (isinstance(lr, torch.Tensor) and lr.is_cuda and lr.dim() == 2 and bool(pipe.get('full_dn', False)) and biaslut is None
             and pipe.get('bias_corr', 'pre') == 'pre' and pipe.get('full_est', True) and DEVICE_CHAIN
             and 'simple' in str(pipe.get('est_type', 'simple')) and 'cal_est' not in pipe
-            and est_fit_of(pipe) == 'lsq')          # (the chain's fit is the least-squares one of yond_frame_params_f64)
+            and est_fit_of(pipe) == 'lsq'           # (the chain's fit is the least-squares one of yond_frame_params_f64)
+            and denoiser_of(pipe) is None)          # ('fbi' normalises by the frame's own min / max: the chain has no such parameter)
 
 
 DEVICE_CHAIN = True                 # (module attribute: tools / tests switch the host-side chain back on for A/B)
@@ -1132,7 +1169,7 @@ def chain_applies_sidd(lr, lr_full, net, arch, pipe, p, biaslut=None):
     return (isinstance(lr, torch.Tensor) and lr.is_cuda and lr.dim() == 3 and lr.shape[0] == 32 and not pipe.get('full_dn', False)
             and biaslut is None and pipe.get('bias_corr', 'pre') == 'pre' and pipe.get('full_est', True) and DEVICE_CHAIN and CHAIN_SIDD
             and 'simple' in str(pipe.get('est_type', 'simple')) and 'cal_est' not in pipe and 'rot_cfa' not in p
-            and est_fit_of(pipe) == 'lsq'
+            and est_fit_of(pipe) == 'lsq' and denoiser_of(pipe) is None
             and (lr_full is None or (isinstance(lr_full, torch.Tensor) and lr_full.is_cuda and lr_full.dim() == 2)))
 
 
@@ -1421,7 +1458,7 @@ def _iter_denoise_pge_blocks(lr, blocks, lr_cat, net, arch, pipe, p, bias_corr, 
     params = [(p['gain'], p['sigma'])]
     vst_type = pipe.get('vst_type', 'exact')
     if pipe.get('full_dn', False):                                                     # :387-389: the mean estimate, no shared LUT
-        raw_dn = VST_Denoiser(lr_cat, p, net, arch, bias_corr, None, vst_type, clip01=True, biaslut=biaslut)
+        raw_dn = VST_Denoiser(lr_cat, p, net, arch, bias_corr, None, vst_type, clip01=True, biaslut=biaslut, denoiser=denoiser_of(pipe))
         return dict(raw_dns=[raw_dn], regs=[reg], params=params)
     bias_func = None
     if bias_corr is not None and biaslut is None:                                      # :392-397: built once, from the mean p
@@ -1437,7 +1474,7 @@ def _iter_denoise_pge_blocks(lr, blocks, lr_cat, net, arch, pipe, p, bias_corr, 
         ps = [dict(p) for _ in range(blocks.shape[0])]
     blk = rot90(blocks, rot_k_) if rot_k_ else blocks
     # with the 2-D table every block takes its own row (bias_func None); else the shared LUT of the mean p
-    outs = VST_Denoiser(blk, ps, net, arch, bias_corr, [bias_func] * blk.shape[0], vst_type, clip01=True, biaslut=biaslut)
+    outs = VST_Denoiser(blk, ps, net, arch, bias_corr, [bias_func] * blk.shape[0], vst_type, clip01=True, biaslut=biaslut, denoiser=denoiser_of(pipe))
     if rot_k_:
         outs = rot90(outs, 4 - rot_k_)
     return dict(raw_dns=[torch.cat(list(outs), dim=-1).contiguous()], regs=[reg], params=params)
@@ -1460,6 +1497,7 @@ def IterDenoise(lr_raw, net, arch, pipe, lr_full=None, p=None, device=None, log=
     if bias_corr == 'none':
         bias_corr = None
     full_dn = bool(pipe.get('full_dn', False))
+    dn_type = denoiser_of(pipe)                # 'fbi': YOND_SIDD.py:266-279 (the host chain: chain_applies* answer False)
     if lr_full is None and 'rot_cfa' not in p:
         lr_c = _dev(lr_raw, device)
         if chain_applies(lr_c, net, arch, pipe, biaslut):
@@ -1539,14 +1577,14 @@ def IterDenoise(lr_raw, net, arch, pipe, lr_full=None, p=None, device=None, log=
 
     def denoise_all(bias_func):
         if full_dn:                                                                    # :387-389
-            return VST_Denoiser(lr_cat, p, net, arch, bias_corr, bias_func, vst_type, clip01=True, lr_max=lr_max, biaslut=biaslut)
+            return VST_Denoiser(lr_cat, p, net, arch, bias_corr, bias_func, vst_type, clip01=True, lr_max=lr_max, biaslut=biaslut, denoiser=dn_type)
         blk = blocks
         if rot_k_:                             # :402-404 / :462-464: every block turned to RGGB around the denoiser
             blk = rot90(blocks, rot_k_)
         if bias_corr is not None:
-            outs = VST_Denoiser(blk, p, net, arch, bias_corr, bias_func, vst_type, clip01=True, biaslut=biaslut)   # one batch-32 forward
+            outs = VST_Denoiser(blk, p, net, arch, bias_corr, bias_func, vst_type, clip01=True, biaslut=biaslut, denoiser=dn_type)   # one batch-32 forward
         else:                                  # no shared LUT: per-block calls as the reference does (:398-407)
-            outs = torch.stack([VST_Denoiser(blk[num], p, net, arch, bias_corr, bias_func, vst_type, clip01=True) for num in range(32)])
+            outs = torch.stack([VST_Denoiser(blk[num], p, net, arch, bias_corr, bias_func, vst_type, clip01=True, denoiser=dn_type) for num in range(32)])
         if rot_k_:
             outs = rot90(outs, 4 - rot_k_)
         return torch.cat(list(outs), dim=-1).contiguous()                              # :408
@@ -1785,6 +1823,8 @@ def denoise_stream_batches(frames, B, net, arch, pipe, p=None, device=None):
     if est_fit_of(pipe) != 'lsq':
         _ransac_stream_note('denoise_stream_batches')
         chain_cfg = False
+    if denoiser_of(pipe) is not None:
+        chain_cfg = False
     if not chain_cfg:
         while True:
             batch = take()
@@ -1886,7 +1926,7 @@ def IterDenoiseBatch(frames, net, arch, pipe, p=None, device=None):
     regs = [e[0] for e in est]
     maxes = [np.float32(e[1]['frame_max']) if 'frame_max' in e[1] else np.float32(_frame_max(f).item()) for e, f in zip(est, lrs)]
     ps = [dict(p0, gain=r[0] * scale, sigma=np.sqrt(max(r[1], 0)) * scale) for r in regs]  # :356
-    raw_dn = VST_Denoiser(stack, ps, net, arch, bias_corr, None, vst_type, clip01=True, lr_max=maxes)
+    raw_dn = VST_Denoiser(stack, ps, net, arch, bias_corr, None, vst_type, clip01=True, lr_max=maxes, denoiser=denoiser_of(pipe))
     raw_dns, all_regs, all_params = [raw_dn], [regs], [[(q['gain'], q['sigma']) for q in ps]]
     alive = [True] * B
     if pipe.get('iter', 'iter') == 'iter':
@@ -1910,7 +1950,7 @@ def IterDenoiseBatch(frames, net, arch, pipe, p=None, device=None):
                 funcs.append(get_bias(maxes[i] * scale, q['sigma'], q['gain'], device=stack.device))   # :450-452
             if not any(alive):
                 break
-            nxt = VST_Denoiser(stack, ps2, net, arch, bias_corr, funcs, vst_type, clip01=True, lr_max=maxes)
+            nxt = VST_Denoiser(stack, ps2, net, arch, bias_corr, funcs, vst_type, clip01=True, lr_max=maxes, denoiser=denoiser_of(pipe))
             for i in range(B):
                 if not alive[i]:
                     nxt[i] = raw_dn[i]
@@ -1926,7 +1966,7 @@ def stream_applies(pipe, p=None, biaslut=None):
     est_type 'simple', 'once' or the shipped 'iter' with max_iter 1) -- the configurations in which `frames` may carry per-frame parameter dicts."""
     ok = (DEVICE_CHAIN and bool(pipe.get('full_dn', False)) and pipe.get('bias_corr', 'pre') == 'pre' and 'simple' in str(pipe.get('est_type', 'simple'))
           and 'cal_est' not in pipe and pipe.get('full_est', True) and 'rot_cfa' not in (p or {}) and biaslut is None
-          and est_fit_of(pipe) == 'lsq')
+          and est_fit_of(pipe) == 'lsq' and denoiser_of(pipe) is None)
     mode = pipe.get('iter', 'iter')
     return ok and (mode == 'once' or (mode == 'iter' and pipe.get('max_iter', 1) == 1 and STREAM_ITER))
 
@@ -1945,6 +1985,11 @@ def denoise_stream(frames, net, arch, pipe, p=None, device=None):
     in the configurations `stream_applies` names."""
     if est_fit_of(pipe) != 'lsq':
         _ransac_stream_note('denoise_stream')
+        for f in frames:
+            f, pk = f if isinstance(f, tuple) else (f, p)
+            yield IterDenoise(f, net, arch, pipe, p=pk, device=device)
+        return
+    if denoiser_of(pipe) is not None:          # 'fbi' (and 'bm3d', which raises): the host chain, frame by frame
         for f in frames:
             f, pk = f if isinstance(f, tuple) else (f, p)
             yield IterDenoise(f, net, arch, pipe, p=pk, device=device)

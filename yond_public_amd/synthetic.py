@@ -27,6 +27,9 @@ def synth_noisy(H, W, K=4.0, sigma=6.0, idx=0, clip=True, scale=959.0):
     return noisy.astype(np.float32), clean.astype(np.float32)
 
 
+_FBI_LIVE_TAPS = {'new1': 8, 'new2': 9, 'new3': 5}      # archs/comp.py:268, 281, 294: the masks' ones
+
+
 def procedural_state_dict(net, seed=0, gain=1.0):
     """Deterministic weights for a yond_public_amd.archs module: per-key seeded generator,
     fan-in-scaled normal weights, small biases, FiLM scales around 1."""
@@ -47,8 +50,15 @@ def procedural_state_dict(net, seed=0, gain=1.0):
                 sd[key] = torch.zeros(shape, dtype=ref.dtype)
             else:
                 sd[key] = torch.randn(shape, generator=g) * 0.1
+        elif 'activation' in key:
+            # a PReLU of FBI_Net (1-D weight): slopes uniform in [-0.1, 0.4] -- the reference's initial 0 would hide a dropped or
+            # mis-indexed slope
+            sd[key] = torch.rand(shape, generator=g) * 0.5 - 0.1
         elif key.endswith('.weight'):
             fan_in = shape[0] if 'upv' in key else shape[1] * shape[2] * shape[3]
+            live = _FBI_LIVE_TAPS.get(key.split('.')[-3] if key.count('.') >= 2 else '')
+            if live is not None and key.endswith('.conv1.weight'):
+                fan_in = shape[1] * live                                # FBI_Net's masked convolutions: the live taps only
             std = gain * math.sqrt(1.0 / fan_in)
             if '.gamma.0' in key or '.sfm1.0' in key or '.sfm2.0' in key:
                 std = 4.0
@@ -113,6 +123,41 @@ def denoising_state_dict(net, seed=0, eps=0.004):
             w[c, :8] = 0
             w[c, 4 + c, 1, 1] = 1.0
             w[c, c, 1, 1] = -1.0
+        return sd
+
+    if name == 'FBI_Net':
+        # out = x / 2 + (mean of the 8 mosaic neighbours) / 2 for `res` (a = 1/2, b = mean / 2), the mean itself otherwise, plus an
+        # eps-sized contribution of everything else.  Feature 0 of new1 is the mean (non-negative behind the VST: every PReLU passes
+        # it); every later masked convolution hands it on through its live centre tap, every residual module halves it
+        # (its 1x1 weights are eps-sized), so layer l adds c_l * mean to the sum, c_1 = 1/2, c_{l+1} = (1 + c_l) / 4; the tail
+        # halves the average C once more and the output layer undoes C / 2.
+        layers = int(net.args['num_of_layers'])
+        for k in sd:
+            if 'activation' not in k:
+                sd[k] = sd[k] * eps
+        sd['new1.new1.conv1.weight'][0] = 1.0 / 8.0
+        sd['new1.new1.conv1.weight'][0, 0, 1, 1] = 0.0                 # (masked: never read)
+        sd['new1.new1.conv1.bias'][0] = 0.0
+        for k in sd:
+            if k.endswith(('new2.conv1.weight', 'new3.conv1.weight')):
+                c = sd[k].shape[-1] // 2
+                sd[k][0] = 0.0
+                sd[k][0, 0, c, c] = 1.0
+                sd[k[:-len('weight')] + 'bias'][0] = 0.0
+        c_l, total = 0.5, 0.5
+        for _ in range(layers - 1):
+            c_l = (1.0 + c_l) / 4.0
+            total += c_l
+        C = total / layers
+        w, b = sd['output_layer.weight'], sd['output_layer.bias']
+        b[:] = 0.0
+        w[:, 0] = 0.0
+        if w.shape[0] == 2:
+            w[1, 0, 0, 0] = 1.0 / C                                    # b = (C mean / 2) / C
+            if net.args['output_type'] == 'linear':
+                b[0] = 0.5                                             # a
+        else:
+            w[0, 0, 0, 0] = 2.0 / C
         return sd
 
     if name == 'UNetSeeInDark':
