@@ -394,14 +394,14 @@ int yond_box_stats_self2_f32(const float* blur2, int h, int w, int k, int tile_w
 int yond_box_stats_collab_f32(const float* bayer_lr, const float* bayer_hr, int H, int W, int k, int tile_w,
                               float* mean, float* var, float* lap, void* stream);
 
-/* (K5' -- the same maps in ONE pass, the B19 map never leaving the chip -- measured slower than K5 + sweep 1 and is built only
- * into experiment libraries: include/yond_hip_experiments.h, `python -m yond_public_amd.build --experiments`.) */
+/* (K5' -- the same maps in ONE pass, the B19 map never leaving the chip -- measured slower than K5 + sweep 1 and was retired:
+ * profiles/r05_experiments/README.md is the record, git history has the source.) */
 
 /* K5+ the hot-path producers of the estimator, one call per frame: the streaming kernels of K5 (stage 1 of the self mode also
  * collects the frame maximum into the workspace head) followed by sweep 1 of the threshold selection (yond_nle_stats_f32
- * below) on the same workspace, which this call resets first.  Same results and same workspace contract as K5';
- * `blur2` [4][H/2][W/2] is scratch (the B19 map).  The default of SimpleNLF: fewer instructions per pixel than K5' at
- * 32 B/px more HBM traffic, which the estimator (issue-bound, not HBM-bound) does not notice.  Any k that K5 takes. */
+ * below) on the same workspace, which this call resets first.  `blur2` [4][H/2][W/2] is scratch
+ * (the B19 map).  The default of SimpleNLF: fewer instructions per pixel than the retired K5' at 32 B/px more HBM traffic,
+ * which the estimator (issue-bound, not HBM-bound) does not notice.  Any k that K5 takes. */
 int yond_box_stats_self_stats_f32(const float* bayer, int H, int W, int k, int k2, int tile_w, float* mean, float* var,
                                   float* blur2, float* lap, const double* q_host, int nq, void* ws, void* stream);
 int yond_box_stats_collab_stats_f32(const float* bayer_lr, const float* bayer_hr, int H, int W, int k, int tile_w,
@@ -423,8 +423,7 @@ int yond_percentiles_f32(const float* data, size_t n, const double* q_host, int 
  * yond_nlf_score3_f64 on the hot path.  `ws`: device workspace of yond_nle_ws_bytes(n) bytes, 16-byte aligned.
  *   yond_nle_stats_f32      sweep 1 over (lap, mean) (n elements as rows of `width`): level-1 histogram of lap and, per
  *                           1/1000 mean bin, the smallest lap (a bin is occupied among lap <= T iff its smallest lap <= T);
- *                           resets the workspace first.  (The experimental one-pass box kernel does the same
- *                           while it produces the maps.)
+ *                           resets the workspace first.
  *   yond_nle_threshold_f32  sweep 2 over lap + finish: the exact order statistics, np.percentile(lap, q, 'linear') ->
  *                           ths; with want_score: npeaks[i], score = ths / (q * npeaks), i* = argmin(score[1:]) + 1 -> sel.
  *                           Needs sweep 1's state in `ws`; may be repeated on it (its own counters are reset when it ends).

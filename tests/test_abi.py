@@ -88,3 +88,17 @@ def test_cpu_tensor_is_rejected_loudly():
     net = GuidedResUnet(dict(name='GuidedResUnet', in_nc=4, out_nc=4, nf=8, nframes=1, res=True, norm=True))
     with pytest.raises(YondHipError):
         net(torch.zeros(1, 4, 32, 32), torch.tensor(0.1))
+
+
+def test_retired_one_pass_box_kernels_are_refused_before_any_work():
+    """SimpleNLF's box='one-pass' (older spelling: fused=True) names kernels that were retired: refused with YondHipError before the
+    frame is looked at -- a frame object that fails on any use never gets used -- and so without a GPU."""
+    from yond_public_amd import pipeline as P
+    from yond_public_amd._lib import YondHipError
+
+    class Untouchable:
+        def __getattr__(self, name):
+            raise AssertionError(f"the frame was used ({name}) before the refusal")
+    for kw in (dict(box='one-pass'), dict(fused=True), dict(box='one-pass', k=13)):
+        with pytest.raises(YondHipError, match="retired"):
+            P.SimpleNLF(Untouchable(), setting={'mode': 'self'}, **kw)

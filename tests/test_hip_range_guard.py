@@ -15,7 +15,6 @@ A kernel that stages or stores an fp32 value as fp16 halves ORs bit 0 into its s
   conv_split.hip       the two device-side weight packers of the training step: a weight beyond 65504 (the single-layer packer is probed
                        below; the batched one applies the same per-element test and is launched by the training-step tests, its flag
                        is not probed on its own)
-  block0_fused.hip     the fused level-0 block: experiment builds of the library only (not in the product build, no test here)
 
 Kernel level: ONE element of a well-scaled tensor replaced, at the first pixel / first channel, the last valid pixel of a ragged
 tile / last real channel, and an interior position: 65000 leaves the word at 0 and the output within the split-operand bound
@@ -43,7 +42,7 @@ DEV = 'cuda:0'
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # file -> number of `atomicOr(<...>status...` / `atomicOr(<...>YOND_STATUS_...` statements the table above accounts for
-SITES = {"conv_split_kernel.h": 1, "conv_s2_tall.hip": 1, "conv.hip": 1, "gemm_split.hip": 2, "wgrad_split.hip": 1, "conv_split.hip": 2, "block0_fused.hip": 1}
+SITES = {"conv_split_kernel.h": 1, "conv_s2_tall.hip": 1, "conv.hip": 1, "gemm_split.hip": 2, "wgrad_split.hip": 1, "conv_split.hip": 2}
 
 
 def test_every_raising_site_is_in_the_table():

@@ -26,12 +26,6 @@ class YondConvDesc(C.Structure):
                 ("in_fmt", i32), ("out_fmt", i32), ("res_fmt", i32), ("clk", vp), ("tile_order", i32), ("dst2", vp)]
 
 
-class YondBlock0Desc(C.Structure):
-    _fields_ = [("x", vp), ("in_fmt", i32), ("N", i32), ("H", i32), ("W", i32), ("w1", vp), ("w2", vp),
-                ("s1", vp), ("t1", vp), ("s2", vp), ("t2", vp), ("ebatch", i32), ("dst", vp),
-                ("out4_w", vp), ("out4_b", vp), ("out4_x", vp), ("out4_ub", vp), ("out4_dst", vp), ("status", vp)]
-
-
 class YondFilmDesc(C.Structure):
     _fields_ = [("kind", i32), ("C", i32), ("ld", i32),
                 ("w_a0", vp), ("b_a0", vp), ("w_a2", vp), ("b_a2", vp), ("w_b0", vp), ("b_b0", vp),
@@ -168,13 +162,6 @@ PROTOTYPES = {
     "yond_rownoise_sums_f32": [vp, i32, i32, vp, vp],
     "yond_rownoise_apply_f32": [vp, vp, i32, i32, vp, i32, i32, f64, f64, vp, vp],
 }
-# experiment builds only (include/yond_hip_experiments.h): bound when the loaded library has them
-EXPERIMENT_PROTOTYPES = {
-    "yond_box_stats_self_fused_f32": [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp],
-    "yond_box_stats_collab_fused_f32": [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp],
-    "yond_block0_fused_f32": [C.POINTER(YondBlock0Desc), vp],          # the fused level-0 block (round 5: measured no-go)
-    "yond_pack_block0_weight_f32": [vp, i32, i32, vp],
-}
 _SIZE_T_RET = {"yond_select_ws_bytes", "yond_nle_ws_bytes", "yond_lut_ws_bytes", "yond_bias_lut_big_scratch", "yond_bias_points_scratch",
                "yond_conv_wgrad_ws_bytes", "yond_conv_wgrad_split_ws_bytes",
                "yond_est_head_ws_bytes", "yond_ransac_compact_ws_bytes", "yond_ransac_ws_bytes",
@@ -205,20 +192,11 @@ def load():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = C.c_size_t if name in _SIZE_T_RET else C.c_int
-    for name, args in EXPERIMENT_PROTOTYPES.items():
-        if hasattr(lib, name):
-            fn = getattr(lib, name)
-            fn.argtypes, fn.restype = args, C.c_int
     if lib.yond_abi_version() != ABI_VERSION:
         raise YondHipError(f"{LIB_PATH} has ABI version {lib.yond_abi_version()}, this package binds version {ABI_VERSION} "
                            "(YondConvDesc layout): rebuild with `python -c 'import __graft_entry__ as g; g.build()'`")
     _lib = lib
     return lib
-
-
-def has(name):
-    """True if the loaded library exports `name` (experiment entry points exist only in -DYOND_EXPERIMENTS builds)."""
-    return hasattr(load(), name)
 
 
 def check(rc, what):

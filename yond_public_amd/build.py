@@ -21,8 +21,7 @@ def sources():
 
 
 def headers():
-    return glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(HERE, "..", "include", "yond_hip.h"),
-                                                   os.path.join(HERE, "..", "include", "yond_hip_experiments.h")]
+    return glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(HERE, "..", "include", "yond_hip.h")]
 
 
 def _obj(src, extra_flags=()):
@@ -182,7 +181,7 @@ EXP_LIB = os.path.join(HERE, "..", "tools", "probe", "libyond_exp.so")
 
 def build_experiments(extra=()):
     """The experiment library (tools/probe/libyond_exp.so): -DYOND_EXPERIMENTS adds the environment switches of the launch
-    heuristics and the measured-and-dropped alternatives (one-pass NLE kernels); use it with YOND_HIP_LIB=<path>."""
+    heuristics (the same-process A/B runs of tools/); use it with YOND_HIP_LIB=<path>."""
     os.makedirs(os.path.dirname(EXP_LIB), exist_ok=True)
     return build_lib(extra_flags=["-DYOND_EXPERIMENTS"] + list(extra), lib=os.path.normpath(EXP_LIB))
 

@@ -64,15 +64,10 @@ extern "C" int SPLIT_DBG_READER(unsigned long long* host) {
 
 __host__ __device__ constexpr int yond_sp_plane_units(int H, int W) { return YOND_SP_PLANE_UNITS(H, W); }
 
-template <int STRIDE, int TH, int TN, int MW, int PARTS, int NWB, bool K1 = false, int FOLD = 0, int NWAVE = 8, int ROLES = 0>
+template <int STRIDE, int TH, int TN, int MW, int PARTS, int NWB, bool K1 = false, int FOLD = 0>
 struct SplitCfg {
-    // NWAVE 8: 512-thread workgroups, two waves per SIMD (every shipped kernel but one); NWAVE 4 (round 6, the stride-2 layer of the split path): ONE wave per
-    // SIMD with twice the registers, so that a wave can own two output rows -- the only way to fewer LDS fragment reads per MFMA that fits the CU's 160 KB
+    static constexpr int NWAVE = 8;                                  // 512-thread workgroups, two waves per SIMD
     static constexpr int NT = 64 * NWAVE;
-    // ROLES 1 (round 6, experiment): the first half of the waves (one per SIMD) only multiply -- they own the accumulators, two output rows each --, the second half
-    // only moves data: global loads, weight DMA, the staging writes.  The multiplying wave's instruction stream is then fragment reads + MFMAs alone
-    static constexpr int NWC = ROLES ? NWAVE / 2 : NWAVE;            // waves that hold accumulators
-    static constexpr int NTS = ROLES ? NT / 2 : NT;                  // threads that stage and issue the memory operations
     static constexpr int KC = 16;
     // K1: the decoder's 1x1 GEMM (ConvTranspose2d 2x2 + cat + 1x1 shortcut folded, engine.py) -- one tap, so a step takes
     // THREE consecutive 16-channel chunks as pseudo-taps (a short step is all overhead); no halo
@@ -92,13 +87,13 @@ struct SplitCfg {
     static constexpr int PIX_ITEMS = IH * IW * 4;                    // staging items of one 16-channel chunk
     static constexpr int W_FLOATS = TAPS * 2 * PARTS * TN * 4;
     static constexpr int RG = TH / MW;                              // row groups of waves
-    static constexpr int NCW = NWC / RG;                            // channel groups of waves
+    static constexpr int NCW = NWAVE / RG;                          // channel groups of waves
     static constexpr int NW = TN / 32 / NCW;                        // 32-channel blocks per wave
     static constexpr int NITEM = NPT * IH * IW * 4;                 // 16-byte (4-channel) staging items per step
     static constexpr int NIN = (NITEM + NT - 1) / NT;
     static constexpr int NWV = W_FLOATS / 4;
-    static constexpr int NWT = (NWV + NTS - 1) / NTS;
-    static constexpr int NWT_MIN = NWV / NTS;                       // LDS-DMA instructions every wave issues per step
+    static constexpr int NWT = (NWV + NT - 1) / NT;
+    static constexpr int NWT_MIN = NWV / NT;                        // LDS-DMA instructions every wave issues per step
     static constexpr int NOPS = NWT + NIN;                          // vector-memory instructions per thread and step
     static constexpr int WAHEAD = NWB - 1;                          // the LDS-DMA of step s fetches weights(s + WAHEAD)
     static constexpr bool LOADS_FIRST = WAHEAD == 2;                // order of a step's memory operations (see the step pipeline)
@@ -106,11 +101,11 @@ struct SplitCfg {
     static constexpr int W4_OFF = 2 * IN_FLOATS + NWB * W_FLOATS;   // floats: 4 x 32 weights of the fused output projection
     // (the projection's weights -- O4 -- and the FiLM vectors -- OSP -- share one region: no kernel has both)
     static constexpr int FILM_OFF = W4_OFF;                         // floats: per wave and 32-channel block {scale[32], shift[32]} (split-plane epilogue)
-    static constexpr int FILM_FLOATS_ = NWC * NW * 64 * (FOLD && STRIDE == 1 ? FOLD : 1);     // (FOLD: every sub-tile may belong to another image; stride 2 never stores split planes)
+    static constexpr int FILM_FLOATS_ = NWAVE * NW * 64 * (FOLD && STRIDE == 1 ? FOLD : 1);     // (FOLD: every sub-tile may belong to another image; stride 2 never stores split planes)
     static constexpr int FILM_FLOATS = (TN == 32 && FILM_FLOATS_ < 128) ? 128 : FILM_FLOATS_;
     // h-only operands (PARTS 1) leave the transposed epilogue no consumed buffer large enough for its scratch (8 waves x 32 pixels x 36 floats):
     // their kernels use little LDS, so the scratch gets a region of its own behind everything else
-    static constexpr int EP_FLOATS_C = NWC * 32 * 36;
+    static constexpr int EP_FLOATS_C = NWAVE * 32 * 36;
     static constexpr bool EP_OWN = PARTS == 1 && STRIDE == 1 && EP_FLOATS_C > ((TN >= 64 && !K1) ? W_FLOATS : IN_FLOATS);
     static constexpr int EP_OFF = FILM_OFF + FILM_FLOATS;
     static constexpr int SMEM_BYTES = (EP_OFF + (EP_OWN ? EP_FLOATS_C : 0)) * 4;  // (W4: the O4 instantiation only; FILM: the split-plane epilogue only)
@@ -123,8 +118,7 @@ struct SplitCfg {
     static constexpr int NDI = (NDS + NWAVE - 1) / NWAVE;           // ... per wave
     static_assert(NWB == 2 || NWB == 3, "two or three weight buffers");
     static_assert(!K1 || (STRIDE == 1 && PIX_ITEMS % NT == 0), "1x1 mode: whole chunks per pass of the staging threads");
-    static_assert((NWAVE == 8 || NWAVE == 4) && RG * NCW == NWC && NW >= 1 && NW * NCW * 32 == TN, "wave grid does not cover the tile");
-    static_assert(!ROLES || (NWAVE == 8 && !K1 && FOLD == 0), "role split: eight waves, the 3x3 forms");
+    static_assert(RG * NCW == NWAVE && NW >= 1 && NW * NCW * 32 == TN, "wave grid does not cover the tile");
     static_assert(FOLD == 0 || FOLD == 2 || FOLD == 4, "folded tiles: two or four sub-tiles");
 };
 
@@ -153,10 +147,10 @@ __device__ __forceinline__ void split_barrier_keep_loads() { asm volatile("s_wai
 // (64-wide tile = 32 channels x two sub-positions) 6 / 11 / 22 steps where two tiles took 8 / 16 / 32.
 // D2 (stride 2): the layer also stores SiLU(value) in split planes (YondConvDesc.dst2), from the same epilogue loop -- an
 // instantiation of its own, so that the kernels without it keep their code and register allocation.
-template <int STRIDE, int TH, int TN, int MW, int PARTS, int NWB, bool PRE, bool O4 = false, bool K1 = false, int ISPM = 0, bool OSP = false, bool S2 = false, bool D2 = false, int FOLD = 0, int NWAVE = 8, int ROLES = 0>
-__global__ __launch_bounds__(64 * NWAVE, (NWAVE == 4 && STRIDE == 1) ? 2 : 1) void conv_split_kernel(const YondConvDesc d) {    // (four waves at stride 1: two workgroups per CU, 256 registers per wave)
-    using C = SplitCfg<STRIDE, TH, TN, MW, PARTS, NWB, K1, FOLD, NWAVE, ROLES>;
-    static_assert(!ROLES || (ISPM == 2 && !OSP && !O4 && !PRE), "role split: the register-staged split-plane input (stride 2)");
+template <int STRIDE, int TH, int TN, int MW, int PARTS, int NWB, bool PRE, bool O4 = false, bool K1 = false, int ISPM = 0, bool OSP = false, bool S2 = false, bool D2 = false, int FOLD = 0>
+__global__ __launch_bounds__(512, 1) void conv_split_kernel(const YondConvDesc d) {
+    using C = SplitCfg<STRIDE, TH, TN, MW, PARTS, NWB, K1, FOLD>;
+    constexpr int NWAVE = C::NWAVE;
     static_assert(!FOLD || (!O4 && !S2 && ((!K1 && STRIDE == 1 && ISPM != 2 && OSP) || (STRIDE == 2 && (ISPM == 2 || (ISPM == 0 && !PRE && !D2))) || (K1 && ISPM == 2) || (!K1 && STRIDE == 1 && ISPM == 0 && !OSP && !PRE))),
                   "folded tiles: the split-plane data flow's kernels (3x3 stride 1: LDS-DMA or register-staged input, split-plane store; stride 2 and the decoder GEMM: register-staged split planes) "
                   "and the plain [N][H][W][C] 3x3 layer (training, UNetSeeInDark)");
@@ -176,24 +170,24 @@ __global__ __launch_bounds__(64 * NWAVE, (NWAVE == 4 && STRIDE == 1) ? 2 : 1) vo
     constexpr int IPP = ISR ? 2 * PARTS : 4;
     constexpr int PIX_ITEMS = C::IH * C::IW * IPP;            // staging items of one 16-channel chunk
     constexpr int NITEM = C::NPT * PIX_ITEMS;                 // ... of a step
-    static_assert(!K1 || PIX_ITEMS % C::NTS == 0, "1x1 mode: whole chunks per pass of the staging threads");
-    constexpr int NIN = ISP ? 0 : (NITEM + C::NTS - 1) / C::NTS;   // register-staged 16-byte items per (staging) thread and step
+    static_assert(!K1 || PIX_ITEMS % C::NT == 0, "1x1 mode: whole chunks per pass of the staging threads");
+    constexpr int NIN = ISP ? 0 : (NITEM + C::NT - 1) / C::NT;     // register-staged 16-byte items per thread and step
     constexpr int NINA = NIN > 0 ? NIN : 1;                  // (array extents)
     constexpr int NDI = ISP ? C::NDI : 0;                    // input LDS-DMAs per wave and step
     // (K1: a thread's items k and k + PIX_ITEMS / NT are the SAME pixel of different 16-channel chunks -- one offset serves both)
-    constexpr int KD = K1 ? PIX_ITEMS / C::NTS : NIN;      // distinct pixels among a thread's register-staged items
+    constexpr int KD = K1 ? PIX_ITEMS / C::NT : NIN;       // distinct pixels among a thread's register-staged items
     // (LDS-DMA input: a slot's unit offset inside its plane depends on the slot's position in the plane only -- slots k and k + DPER
     // of a wave address the same units of different planes)
     constexpr int DPER = C::WPP / split_gcd(C::WPP, NWAVE);
     constexpr int NG = ISP ? (NDI < DPER ? NDI : DPER) : KD;  // per-tile offsets a thread keeps
     constexpr int NOPS = C::NWT + NIN + NDI;                 // vector-memory instructions per thread and step
-    constexpr int KEEP = (ISP || ROLES) ? (C::WAHEAD == 2 ? C::NWT_MIN : 0) : (C::WAHEAD == 2 ? NIN + C::NWT_MIN : NIN);   // memory operations that may stay in flight across a barrier
+    constexpr int KEEP = ISP ? (C::WAHEAD == 2 ? C::NWT_MIN : 0) : (C::WAHEAD == 2 ? NIN + C::NWT_MIN : NIN);   // memory operations that may stay in flight across a barrier
     extern __shared__ __attribute__((aligned(16))) float smem[];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // ROLES: the staging / memory work belongs to the second half of the workgroup (stid = its thread index there; the multiplying half never uses what it derives from it)
-    const int stid = ROLES ? tid - C::NTS : tid;
-    const bool consumer = !ROLES || __builtin_amdgcn_readfirstlane(wave) < C::NWC;
+    // the thread's index in the staging and memory work (every thread takes part: = tid).  A variable of its own on purpose: with `tid` itself captured by decode and
+    // issue_dma the compiler orders the operands of one scalar AND in every kernel's prologue the other way -- kept so that the generated code stays what was measured
+    const int stid = tid;
     const int li = lane & 31, lh = lane >> 5;
     // FOLD: lane li of a fragment = column li % FSW of sub-tile li / FSW; in the LDS row every sub-tile has its own two halo columns
     constexpr int FSW = FOLD ? 32 / FOLD : 32;
@@ -244,7 +238,7 @@ __global__ __launch_bounds__(64 * NWAVE, (NWAVE == 4 && STRIDE == 1) ? 2 : 1) vo
     int in_lds[NINA];
 #pragma unroll
     for (int k = 0; k < NIN; ++k) {
-        const int it = stid + k * C::NTS;
+        const int it = stid + k * C::NT;
         const int pt = it / PIX_ITEMS;                      // pseudo-tap (K1; 0 otherwise)
         const int pix = (it % PIX_ITEMS) / IPP;
         const int py = pix / C::IW, px = pix % C::IW;
@@ -335,7 +329,7 @@ __global__ __launch_bounds__(64 * NWAVE, (NWAVE == 4 && STRIDE == 1) ? 2 : 1) vo
         if constexpr (ISPM == 0 && !OSP && !K1) asm volatile("" : "+v"(tid_g));
 #pragma unroll
         for (int k = 0; k < KD; ++k) {
-            const int it = tid_g + k * C::NTS;
+            const int it = tid_g + k * C::NT;
             const int pix = (it % PIX_ITEMS) / IPP;
             const int py = pix / C::IW, px = pix % C::IW;
             int gy = K1 ? T.oy0 + py : T.oy0 * STRIDE - 1 + py, gx = K1 ? T.ox0 + px : T.ox0 * STRIDE - 1 + px;
@@ -368,9 +362,7 @@ __global__ __launch_bounds__(64 * NWAVE, (NWAVE == 4 && STRIDE == 1) ? 2 : 1) vo
     // input(s+3) during step s+2, so a load has two steps to arrive.
     // (three rows per wave: 96 accumulator registers leave room for two sets; likewise the h-only stride-2 layer on 128-channel tiles -- 64 accumulator
     // registers, two weight-fragment sets of two blocks: with three sets it spills five registers)
-    // (ROLES: ONE set -- the moving half loads input(s+1) and stages it within step s: it has nothing else to do while the other half multiplies, and a second set
-    // would not fit beside the accumulators: both roles' registers are allocated together)
-    constexpr int NSET = ROLES ? 1 : (MW >= 3 || (STRIDE == 2 && PARTS == 1 && TN == 128)) ? 2 : 3;
+    constexpr int NSET = (MW >= 3 || (STRIDE == 2 && PARTS == 1 && TN == 128)) ? 2 : 3;
     static_assert(NSET == 3 || C::WAHEAD == 1, "the two-set pipeline goes with two weight buffers");
     f32x4 vin[NSET][NINA];
     unsigned vin_ok[NSET] = {};
@@ -418,7 +410,7 @@ __global__ __launch_bounds__(64 * NWAVE, (NWAVE == 4 && STRIDE == 1) ? 2 : 1) vo
     };
     auto issue_load = [&](auto pc, auto kc, const Tile& T, const LoadSrc& L) {
         constexpr int P = decltype(pc)::value, k = decltype(kc)::value;
-        constexpr int t = K1 ? (k * C::NTS) / PIX_ITEMS : 0;  // the item's chunk (K1: PIX_ITEMS is a multiple of the thread count)
+        constexpr int t = K1 ? (k * C::NT) / PIX_ITEMS : 0;   // the item's chunk (K1: PIX_ITEMS is a multiple of the thread count)
         constexpr int kd = k % KD;                             // (K1: the item's pixel)
         const bool ok = T.goff[kd] >= 0;                       // outside the image: read pixel 0, zeroed at the LDS write
         int po = T.goff[kd];
@@ -444,11 +436,11 @@ __global__ __launch_bounds__(64 * NWAVE, (NWAVE == 4 && STRIDE == 1) ? 2 : 1) vo
         constexpr int k = decltype(kc)::value;
         if (wskip) return;
         const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)wbuf;
-        const int it = stid + k * C::NTS;
+        const int it = stid + k * C::NT;
         const int it_wave = __builtin_amdgcn_readfirstlane(it - lane);
         const unsigned lds_wave = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)it_wave * 16u);
         const unsigned voff = (unsigned)it * 16u;
-        if (C::NWV % C::NTS == 0 || it_wave < C::NWV)
+        if (C::NWV % C::NT == 0 || it_wave < C::NWV)
             asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_wave), "v"(voff), "s"(wsrc) : "memory");
     };
     // ISP: the planes of a step's chunk(s), wave-uniform: [n][chunk][half][part][PS units]; DMA slot k of this wave moves the
@@ -548,7 +540,7 @@ __global__ __launch_bounds__(64 * NWAVE, (NWAVE == 4 && STRIDE == 1) ? 2 : 1) vo
     // (the step's cursor arithmetic -- `prep`, which sets wsrc_s / ls_s and may decode the next tile -- runs after the
     // first groups of MFMAs have been issued; memory instructions and staging start at group Q0)
     const float* wsrc_s = nullptr;
-    const bool wave_hi = NWAVE == 8 && __builtin_amdgcn_readfirstlane(wave) >= 4;       // (one wave per SIMD: no partner to arbitrate with)
+    const bool wave_hi = __builtin_amdgcn_readfirstlane(wave) >= 4;
     LoadSrc ls_s = {};
     InSrc is_s = {};
     int dbg_step = 0;
@@ -563,7 +555,7 @@ __global__ __launch_bounds__(64 * NWAVE, (NWAVE == 4 && STRIDE == 1) ? 2 : 1) vo
         // weight fragments of a column: two sets (the next column is fetched during the current one), or -- three rows per
         // wave, register budget -- ONE set, each dy refilled for the next column right behind its last use (two groups ahead
         // of its next use)
-        constexpr bool WINPLACE = MW >= 3 || ROLES != 0;      // (ROLES: the register budget holds both roles)
+        constexpr bool WINPLACE = MW >= 3;
         constexpr int WS = WINPLACE ? 1 : 2;
         f16x8 xr[XD][PARTS], wt[WS][3][C::NW][PARTS];
         auto loadX = [&](auto qc) {
@@ -614,7 +606,7 @@ __global__ __launch_bounds__(64 * NWAVE, (NWAVE == 4 && STRIDE == 1) ? 2 : 1) vo
             // one, which then runs alone and exposes its LDS latencies: the younger half leads for the first half instead
             if constexpr (q == 0) { if (wave_hi) __builtin_amdgcn_s_setprio(1); }
             if constexpr (q == NQ / 2) { if (wave_hi) __builtin_amdgcn_s_setprio(0); }
-            if constexpr (q == Q0 - 1 && !ROLES) prep();
+            if constexpr (q == Q0 - 1) prep();
             if constexpr (q == NQ / 4) SDBG(8);
             if constexpr (q == NQ / 2) SDBG(9);
             if constexpr (q == (3 * NQ) / 4) SDBG(10);
@@ -625,8 +617,7 @@ __global__ __launch_bounds__(64 * NWAVE, (NWAVE == 4 && STRIDE == 1) ? 2 : 1) vo
             // it goes into the first half of the step)
             constexpr int NQO = (ISP && C::WAHEAD == 1) ? (NQW + 1) / 2 : NQW;
             constexpr int qo = qq < NQO ? qq : NQO;
-            // (ROLES: the multiplying waves issue no memory operation and stage nothing)
-            constexpr int o_lo = (q >= Q0 && !ROLES) ? (qo * NOPS + NQO - 1) / NQO : 0, o_hi = (q >= Q0 && !ROLES) ? ((qo + 1 < NQO ? qo + 1 : NQO) * NOPS + NQO - 1) / NQO : 0;
+            constexpr int o_lo = q >= Q0 ? (qo * NOPS + NQO - 1) / NQO : 0, o_hi = q >= Q0 ? ((qo + 1 < NQO ? qo + 1 : NQO) * NOPS + NQO - 1) / NQO : 0;
             static_for<o_lo, o_hi>([&](auto oc) {
                 constexpr int o = decltype(oc)::value;
                 if constexpr (ISP) {
@@ -642,7 +633,7 @@ __global__ __launch_bounds__(64 * NWAVE, (NWAVE == 4 && STRIDE == 1) ? 2 : 1) vo
                 }
             });
             // this group's share of the staging work (element tasks e_lo .. e_hi of the set loaded during the previous step)
-            constexpr int e_lo = (q >= Q0 && !ROLES) ? qq * NE / NQW : 0, e_hi = (q >= Q0 && !ROLES) ? (qq + 1) * NE / NQW : 0;
+            constexpr int e_lo = q >= Q0 ? qq * NE / NQW : 0, e_hi = q >= Q0 ? (qq + 1) * NE / NQW : 0;
             static_for<e_lo, e_hi>([&](auto ec) { stage_task(pc, ec, ob); });
             constexpr int nfin = (e_hi + 0) / 4 - (e_lo + 0) / 4;                     // items completed in this group
             // Issue order of the group: its LDS reads first (they are two groups / one column ahead of their use), then
@@ -1140,7 +1131,7 @@ __global__ __launch_bounds__(64 * NWAVE, (NWAVE == 4 && STRIDE == 1) ? 2 : 1) vo
     // prologue, in the steady-state order of the memory operations (DMA of a step before its loads):
     //   loads input(0) | DMA weights(0), loads input(1) | stage input(0) | DMA weights(1), loads input(2)
     const Cur c1 = adv(cs), c2 = adv(c1);
-    if constexpr (!ISP) { if (!ROLES || !consumer) load_all(IntC<0>{}, cs); }
+    if constexpr (!ISP) load_all(IntC<0>{}, cs);
     Cur cl, cw;                                 // cursors of the step's loads / weight DMA
     if constexpr (ISP) {
         // split-plane input: input(0), weights(0) (, weights(1)); step s issues the DMA of input(s+1) and of weights(s + WAHEAD)
@@ -1150,14 +1141,6 @@ __global__ __launch_bounds__(64 * NWAVE, (NWAVE == 4 && STRIDE == 1) ? 2 : 1) vo
         cl = c1;
         cw = C::WAHEAD == 2 ? c2 : c1;
         split_barrier_keep_loads<C::WAHEAD == 2 ? C::NWT_MIN : 0>();
-    } else if constexpr (ROLES != 0) {
-        if (!consumer) {
-            dma_all(cs, w0);
-            write_in(IntC<0>{}, ibuf);
-        }
-        cl = c1;
-        cw = c1;
-        split_barrier_keep_loads<0>();
     } else if constexpr (NSET == 2) {
         // two register sets (and two weight buffers): set s % 2 receives input(s+2) during step s, staged in step s+1
         dma_all(cs, w0);
@@ -1209,18 +1192,7 @@ __global__ __launch_bounds__(64 * NWAVE, (NWAVE == 4 && STRIDE == 1) ? 2 : 1) vo
             wsrc_s = weight_src(ct_of(cw, cur.ct), cw.ch);
         };
         SDBG(1);
-        if constexpr (ROLES != 0) {
-            if (consumer) {
-                if (computes) mfma_stage(IntC<0>{}, IntC<0>{}, ibuf, w0, obuf, w1, lt, prep);
-            } else {
-                // the moving half: the weight DMA of step s+1 and the loads of input(s+1), which it stages as soon as they arrive -- all of it under the other
-                // half's MFMAs of step s
-                prep();
-                static_for<0, C::NWT>([&](auto kc) { issue_dma(kc, wsrc_s, w1); });
-                static_for<0, NIN>([&](auto kc) { issue_load(IntC<0>{}, kc, lt, ls_s); });
-                write_in(IntC<0>{}, obuf);
-            }
-        } else if (computes) mfma_stage(IntC<(S + 1) % NSET>{}, IntC<S>{}, ibuf, w0, obuf, C::WAHEAD == 2 ? w2 : w1, lt, prep);
+        if (computes) mfma_stage(IntC<(S + 1) % NSET>{}, IntC<S>{}, ibuf, w0, obuf, C::WAHEAD == 2 ? w2 : w1, lt, prep);
         SDBG(2);
         SDBG(3);
         split_barrier_keep_loads<KEEP>();                       // weights(s+1) have landed, input(s+1) is written
@@ -1228,7 +1200,7 @@ __global__ __launch_bounds__(64 * NWAVE, (NWAVE == 4 && STRIDE == 1) ? 2 : 1) vo
         if (last_ch) {
             // scratch: weights(s) / input(s), which no wave reads any more; the barrier behind the epilogue keeps the next
             // step's DMA and staging writes (of OTHER waves) out of it until every wave has read its block back
-            if (computes && consumer) {
+            if (computes) {
                 if constexpr (OSP) {
                     // straight-line variants: the residual blocks' conv1 (FiLM + SiLU) and conv2 (FiLM + residual), a plain layer
                     // with LeakyReLU; the rest generic
@@ -1302,12 +1274,12 @@ __global__ __launch_bounds__(64 * NWAVE, (NWAVE == 4 && STRIDE == 1) ? 2 : 1) vo
     }
 }
 
-template <int STRIDE, int TH, int TN, int MW, int PARTS, int NWB, bool PRE, bool O4 = false, bool K1 = false, int ISP = 0, bool OSP = false, bool S2 = false, bool D2 = false, int FOLD = 0, int NWAVE = 8, int ROLES = 0>
+template <int STRIDE, int TH, int TN, int MW, int PARTS, int NWB, bool PRE, bool O4 = false, bool K1 = false, int ISP = 0, bool OSP = false, bool S2 = false, bool D2 = false, int FOLD = 0>
 int launch_split(const YondConvDesc& d, hipStream_t st) {
-    using C = SplitCfg<STRIDE, TH, TN, MW, PARTS, NWB, K1, FOLD, NWAVE, ROLES>;
+    using C = SplitCfg<STRIDE, TH, TN, MW, PARTS, NWB, K1, FOLD>;
     static_assert(C::SMEM_BYTES <= 160 * 1024, "LDS budget");
     static bool attr_set = false;
-    auto kern = conv_split_kernel<STRIDE, TH, TN, MW, PARTS, NWB, PRE, O4, K1, ISP, OSP, S2, D2, FOLD, NWAVE, ROLES>;
+    auto kern = conv_split_kernel<STRIDE, TH, TN, MW, PARTS, NWB, PRE, O4, K1, ISP, OSP, S2, D2, FOLD>;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM_BYTES);
         if (e != hipSuccess) return (int)e;
@@ -1317,9 +1289,7 @@ int launch_split(const YondConvDesc& d, hipStream_t st) {
     const long long total = FOLD ? (long long)(d.Cout / TN) * (((long long)d.N * ((d.Ho + TH - 1) / TH) * ((d.Wo + FSWL - 1) / FSWL) + FOLD - 1) / (FOLD ? FOLD : 1))
                                  : (long long)(d.Cout / TN) * ((d.Wo + 31) / 32) * ((d.Ho + TH - 1) / TH) * d.N;
     if (total > 0x7fffffffLL) return YOND_EUNSUPPORTED;
-    // (four-wave workgroups whose LDS fits twice into a CU: two persistent workgroups per CU -- one's epilogue and prologue under the other's MFMAs)
-    constexpr int PER_CU = (NWAVE == 4 && C::SMEM_BYTES <= 80 * 1024) ? 2 : 1;
-    const int gmax = (int)yond_exp_long("YOND_SPLIT_GRID", 256) * PER_CU;  // (experiment builds: fewer workgroups than CUs, leaving CUs to a side stream's kernels)
+    const int gmax = (int)yond_exp_long("YOND_SPLIT_GRID", 256);  // (experiment builds: fewer workgroups than CUs, leaving CUs to a side stream's kernels)
     const int grid = total < gmax ? (int)total : gmax;            // one persistent workgroup per CU
     hipLaunchKernelGGL(kern, dim3(grid), dim3(C::NT), C::SMEM_BYTES, st, d);
     YOND_LAUNCH_CHECK();
@@ -1427,19 +1397,7 @@ int launch_split(const YondConvDesc& d, hipStream_t st) {
 #define SPLIT_GROUP_H_TALL4(X)                                                                          \
     X(1, 32, 32, 4, 1, 2, false, false, false, true, true)                                               \
     X(1, 16, 64, 4, 1, 2, true, false, false, false, true) X(1, 16, 64, 4, 1, 2, false, false, false, true, true)
-// round 6, the split path's stride-2 layers with ONE wave per SIMD (256 threads): two output rows per wave (0.89 instead of 1.33 KiB of LDS fragments per MFMA) in the
-// same 4 x 32 x 64 tile and the same LDS
-#define SPLIT_GROUP_S2_W4(X)                                                                            \
-    X(2, 4, 64, 2, 2, 2, false, false, false, 2, false, false, false, 0, 4) X(2, 4, 64, 2, 2, 2, false, false, false, 2, false, false, true, 0, 4)
-// ... and with eight waves in two roles: four multiply (two output rows each), four move the data
-#define SPLIT_GROUP_S2_ROLES(X)                                                                         \
-    X(2, 4, 64, 2, 2, 2, false, false, false, 2, false, false, false, 0, 8, 1) X(2, 4, 64, 2, 2, 2, false, false, false, 2, false, false, true, 0, 8, 1)
-// round 6, level 0 (32 -> 32 channels, resident weights): HALF-SIZE workgroups -- four waves (one per SIMD) on 8 x 32-pixel tiles, 80 KB of LDS, TWO per CU (512
-// persistent workgroups): a level-0 tile has two 16-channel steps and a full epilogue, and with one workgroup per CU nothing runs under its epilogue, its first
-// loads and its barriers (stamps: ~19 k cycles per tile for ~7 k of matrix pipe); two independent workgroups were meant to drift apart and fill each other's gaps.
-// Measured (same box): conv1 2-7 % SLOWER, conv2 equal, the last convolution 4 % faster, the frame 2 % slower -- experiment builds only
-#define SPLIT_GROUP_WRES_W4(X)                                                                          \
-    X(1, 8, 32, 2, 2, 2, true, false, false, false, true, false, false, 0, 4) X(1, 8, 32, 2, 2, 2, false, false, false, true, true, false, false, 0, 4) \
-    X(1, 8, 32, 2, 2, 2, false, true, false, true, false, false, false, 0, 4)
+// (measured slower and retired, source in git history: the stride-2 layers with one wave per SIMD or with multiplying / moving wave roles -- profiles/r06_experiments/README.md,
+// s2_*_ab.txt -- and level 0's half-size workgroups, two per CU -- profiles/r06_experiments/README.md, DESIGN.md sections 0 and 8)
 #define SPLIT_INSTANTIATE(...) template int launch_split<__VA_ARGS__>(const YondConvDesc&, hipStream_t);
 #define SPLIT_EXTERN(...) extern template int launch_split<__VA_ARGS__>(const YondConvDesc&, hipStream_t);

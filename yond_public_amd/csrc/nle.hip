@@ -68,19 +68,15 @@ __device__ __forceinline__ void box_store8(float* __restrict__ p, const float (&
 // 2: collab (mean, var, lap from noisy + denoised Bayer frames)
 // STATS (MODE 0): stage 1 reads every pixel of the frame as an entering pixel, so it also collects the frame maximum
 // (lr.max() for the bias LUT grid, YOND_SIDD.py:256/393) into st->frame_max_key.
-// ROLES (experiment): 512 threads -- waves 0-3 only walk the columns (running sums of batch i into LDS buffer i & 1), waves 4-7 only
-// run the task phase (window sums of batch i - 1 from the other buffer): the two phases of consecutive batches overlap inside one
-// workgroup behind ONE barrier per batch, at twice the LDS (one workgroup per CU instead of two).
-template <int MODE, int KT, int K2T, bool STATS, int BB, bool ROLES = false>
-__global__ __launch_bounds__(ROLES ? 512 : BX_T, ROLES ? 1 : (MODE == 1 ? 4 : 2)) void box_slide_kernel(BoxSrc a, BoxSrc b, BoxGeom g, float* __restrict__ o0,
+template <int MODE, int KT, int K2T, bool STATS, int BB>
+__global__ __launch_bounds__(BX_T, MODE == 1 ? 4 : 2) void box_slide_kernel(BoxSrc a, BoxSrc b, BoxGeom g, float* __restrict__ o0,
                                                         float* __restrict__ o1, float* __restrict__ o2, NleState* st) {
     static_assert(!STATS || MODE == 0, "only stage 1 collects the frame maximum");
     constexpr int NQ = MODE == 0 ? 3 : (MODE == 1 ? 2 : 4);      // running sums per column and plane
     constexpr int NI = MODE == 2 ? 2 : 1;                        // input frames
     constexpr int NL = MODE == 0 ? 3 : 2;                        // loads per input and row: entering, leaving (k), leaving (k2)
-    extern __shared__ __attribute__((aligned(16))) double s_v[]; // [NQ][BB][2][BX_VW]   (ROLES: two of them)
-    const int role = ROLES ? (int)(threadIdx.x >> 8) : -1;       // (wave-uniform) 0: column waves, 1: task waves
-    const int tid = ROLES ? (int)(threadIdx.x & 255) : (int)threadIdx.x;
+    extern __shared__ __attribute__((aligned(16))) double s_v[]; // [NQ][BB][2][BX_VW]
+    const int tid = (int)threadIdx.x;
     const int h = g.h, w = g.w;
     const int k = KT > 0 ? KT : g.k, k2 = MODE == 0 ? (K2T > 0 ? K2T : g.k2) : k;
     const int R = k / 2, R2 = k2 / 2;
@@ -277,31 +273,14 @@ __global__ __launch_bounds__(ROLES ? 512 : BX_T, ROLES ? 1 : (MODE == 1 ? 4 : 2)
             }
         }
     };
-    if constexpr (ROLES) {
-        constexpr int BUF = NQ * BB * 2 * BX_VW;                 // doubles per buffer
-        const int nbatch = (nsteps + BB - 1) / BB;
-        if (role == 0) load_batch(nxt, 0);
-        for (int i = 0; i <= nbatch; ++i) {
-            if (role == 0) {
-                if (i < nbatch) col_phase(i * BB, s_v + (i & 1) * BUF);
-            } else if (i >= 1) {
-                const int l0 = (i - 1) * BB;
-                const bool warm = l0 + BB <= kl_min && l0 + BB <= first_out;
-                if (!warm) task_phase(l0, s_v + ((i - 1) & 1) * BUF);
-            }
-            __syncthreads();
-        }
-    } else {
-        load_batch(nxt, 0);
-        for (int l0 = 0; l0 < nsteps; l0 += BB) {
-            if (col_phase(l0, s_v)) continue;
-            __syncthreads();
-            task_phase(l0, s_v);
-            __syncthreads();
-        }
+    load_batch(nxt, 0);
+    for (int l0 = 0; l0 < nsteps; l0 += BB) {
+        if (col_phase(l0, s_v)) continue;
+        __syncthreads();
+        task_phase(l0, s_v);
+        __syncthreads();
     }
     if constexpr (STATS) {
-        if (ROLES && role != 0) return;                           // (the column waves saw the pixels)
         fmax_ = wave_max(fmax_);
         // a few thousand waves, one word: look first (a coherent load) -- after the first few arrivals nearly nobody has to write
         if ((tid & 63) == 0 && fmax_ > -INFINITY) {
@@ -320,19 +299,19 @@ static int box_args_ok(int h, int w, int k, int tile_w) {
     return YOND_OK;
 }
 
-template <int MODE, int KT, int K2T, bool STATS, int BB, bool ROLES = false>
+template <int MODE, int KT, int K2T, bool STATS, int BB>
 static int launch_box_k(const BoxSrc& a, const BoxSrc& b, const BoxGeom& g, dim3 grid, float* o0, float* o1, float* o2, hipStream_t st,
                         NleState* state) {
     constexpr int NQ = MODE == 0 ? 3 : (MODE == 1 ? 2 : 4);
-    constexpr size_t smem = (size_t)NQ * BB * 2 * BX_VW * sizeof(double) * (ROLES ? 2 : 1);
+    constexpr size_t smem = (size_t)NQ * BB * 2 * BX_VW * sizeof(double);
     static bool attr_set = false;
-    auto kern = box_slide_kernel<MODE, KT, K2T, STATS, BB, ROLES>;
+    auto kern = box_slide_kernel<MODE, KT, K2T, STATS, BB>;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         if (e != hipSuccess) return (int)e;
         attr_set = true;
     }
-    hipLaunchKernelGGL(kern, grid, dim3(ROLES ? 512 : BX_T), smem, st, a, b, g, o0, o1, o2, state);
+    hipLaunchKernelGGL(kern, grid, dim3(BX_T), smem, st, a, b, g, o0, o1, o2, state);
     YOND_LAUNCH_CHECK();
     return YOND_OK;
 }
@@ -350,8 +329,7 @@ static int launch_box(BoxSrc a, BoxSrc b, int h, int w, int k, int k2, int tile_
     g.ow_nom = (((bw + g.nstrip - 1) / g.nstrip) + BX_C - 1) / BX_C * BX_C;
     if (g.ow_nom > maxow) g.ow_nom = maxow;
     // row segments: one round of the workgroups the chip holds (two per CU); longer segments re-read fewer halo rows
-    const bool roles = MODE != 2 && yond_exp_long("YOND_BOX_ROLES", 0) != 0;      // (experiment builds: the role-split form)
-    const long target = yond_exp_long("YOND_BOX_WGS", roles ? (MODE == 1 ? 512 : 256) : (MODE == 1 ? 1024 : 512));
+    const long target = yond_exp_long("YOND_BOX_WGS", MODE == 1 ? 1024 : 512);
     const long cols = 2L * nblk * g.nstrip;
     long nseg = (target + cols / 2) / cols;
     if (nseg < 1) nseg = 1;
@@ -363,10 +341,6 @@ static int launch_box(BoxSrc a, BoxSrc b, int h, int w, int k, int k2, int tile_
     // rows per batch: 4 (LDS per workgroup 55 / 37 / 74 KB: two / four / two workgroups per CU).  Two rows per batch and more
     // workgroups measured slower (self stage 1: 101 us against 70): the task phase is latency bound per wave, and half the lanes idle
     constexpr int BB = 4;
-#ifdef YOND_EXPERIMENTS
-    if constexpr (MODE != 2)
-        if (roles && k == 29 && (MODE != 0 || k2 == 19)) return launch_box_k<MODE, 29, 19, STATS, BB, true>(a, b, g, grid, o0, o1, o2, st, state);
-#endif
     if (k == 29 && (MODE != 0 || k2 == 19)) return launch_box_k<MODE, 29, 19, STATS, BB>(a, b, g, grid, o0, o1, o2, st, state);
     return launch_box_k<MODE, 0, 0, STATS, BB>(a, b, g, grid, o0, o1, o2, st, state);
 }

@@ -675,13 +675,21 @@ def SimpleNLF(lr_raw, hr_raw=None, k=29, setting=None, full=False, device=None, 
     box selects the kernels that produce the three maps:
       'two-pass' (default)  the streaming box kernels with the first sweep of the threshold selection folded into the
                             producer of the lap map and the frame maximum into stage 1 (nle.hip, STATS);
-      'one-pass'            one kernel per frame that keeps the B19 map in LDS (nle_fused.hip; k == 29 only);
+      'one-pass'            refused: the kernel that kept the B19 map in LDS measured slower than the default and was retired
+                            (profiles/r05_experiments/README.md);
       'plain'               the stand-alone kernels of the first version, followed by a separate statistics sweep (kept
                             for the function seam and as a cross-check).
     `fused` is the older spelling (True -> 'one-pass', False -> 'plain').  With full=True the info dict carries
     'frame_max' (float32 maximum of lr_raw) except on the 'plain' path.
     setting['fit'] = 'ransac' replaces the least-squares line of :86 / :114 by polyfit(..., ransac=True) on the same points
     (info['ransac']: winner, counts, threshold and the trial table); 'lsq' is the default."""
+    if box is None:
+        box = 'two-pass' if fused is None else ('one-pass' if fused else 'plain')
+    if box == 'one-pass':                     # (refused before the library is loaded or a tensor is moved)
+        raise L.YondHipError("box='one-pass' (fused=True): the one-pass kernels measured slower than the default producers and were retired "
+                             "(profiles/r05_experiments/README.md; the source is in git history) -- use 'two-pass' or 'plain'")
+    if box not in ('two-pass', 'plain'):
+        raise ValueError(f"box={box!r}")
     setting = setting or {'mode': 'self'}
     lib = L.load()
     lr = _dev(lr_raw, device)
@@ -694,15 +702,6 @@ def SimpleNLF(lr_raw, hr_raw=None, k=29, setting=None, full=False, device=None, 
     mean, var, lap = new(), new(), new()
     st = L.stream()
     k2 = k // 3 * 2 + 1
-    if box is None:
-        box = 'two-pass' if fused is None else ('one-pass' if fused else 'plain')
-    if box == 'one-pass' and k != 29:         # the one-pass kernel is built for the estimator's windows (29, 19)
-        box = 'two-pass'
-    if box == 'one-pass' and not L.has("yond_box_stats_self_fused_f32"):
-        raise L.YondHipError("box='one-pass' needs an experiment build of the library (python -m yond_public_amd.build --experiments; "
-                             "the one-pass kernels measured slower than the default producers and are not in the product)")
-    if box not in ('two-pass', 'one-pass', 'plain'):
-        raise ValueError(f"box={box!r}")
     ws = None
     q = np.ascontiguousarray(QUANTS, dtype=np.float64)
     qp = C.c_void_p(q.ctypes.data)
@@ -710,10 +709,7 @@ def SimpleNLF(lr_raw, hr_raw=None, k=29, setting=None, full=False, device=None, 
         ws = _nle_workspace(4 * h * w, lr.device)
     if setting['mode'] == 'self':
         with _stage("nle_box_self"):
-            if box == 'one-pass':
-                L.check(lib.yond_box_stats_self_fused_f32(L.ptr(lr), H, W, k, k2, tile_w, L.ptr(mean), L.ptr(var), L.ptr(lap),
-                                                          qp, len(q), L.ptr(ws), st), "yond_box_stats_self_fused_f32")
-            elif box == 'two-pass':
+            if box == 'two-pass':
                 blur2 = new()
                 L.check(lib.yond_box_stats_self_stats_f32(L.ptr(lr), H, W, k, k2, tile_w, L.ptr(mean), L.ptr(var), L.ptr(blur2),
                                                           L.ptr(lap), qp, len(q), L.ptr(ws), st), "yond_box_stats_self_stats_f32")
@@ -727,10 +723,7 @@ def SimpleNLF(lr_raw, hr_raw=None, k=29, setting=None, full=False, device=None, 
         if hr.shape != lr.shape:
             raise L.YondHipError("collab NLF needs noisy and denoised frames of the same shape")
         with _stage("nle_box_collab"):
-            if box == 'one-pass':
-                L.check(lib.yond_box_stats_collab_fused_f32(L.ptr(lr), L.ptr(hr), H, W, k, tile_w, L.ptr(mean), L.ptr(var),
-                                                            L.ptr(lap), qp, len(q), L.ptr(ws), st), "yond_box_stats_collab_fused_f32")
-            elif box == 'two-pass':
+            if box == 'two-pass':
                 L.check(lib.yond_box_stats_collab_stats_f32(L.ptr(lr), L.ptr(hr), H, W, k, tile_w, L.ptr(mean), L.ptr(var),
                                                             L.ptr(lap), qp, len(q), L.ptr(ws), st), "yond_box_stats_collab_stats_f32")
             else:
