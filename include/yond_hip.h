@@ -278,6 +278,11 @@ int yond_pack_conv_split_weight_f32(const float* w, int cout, int cin, int ksize
 int yond_gemm_k1_stationary_supported(const YondConvDesc* desc);
 /* 1 if the stride-2 layer described by `desc` (filled in for algo 3) may run with algo = 7 instead (csrc/conv_s2_tall.hip), else 0. */
 int yond_conv_s2_tall_supported(const YondConvDesc* desc);
+/* Which instantiation of the split-operand kernel yond_conv2d_f32 launches for `desc` (algo 3 or 4): its index in the table of variants
+ * (csrc/conv_split_kernel.h), or the negative error code the launch would return.  Host arithmetic on the descriptor's numbers only: no pointer is
+ * dereferenced, no GPU needed.  yond_conv_split_variant_name: the variant's name (its tile, operands, staging, output and extras), NULL outside the table. */
+int yond_conv_split_variant(const YondConvDesc* desc);
+const char* yond_conv_split_variant_name(int variant);
 /* The same packing on the device (w and dst are device pointers; asynchronous on `stream`): the training step re-packs the
  * weights it has just updated without a host round trip.  A weight outside fp16's range sets bit 0 of *status (device int,
  * may be NULL) instead of failing the call. */

@@ -60,6 +60,8 @@ PROTOTYPES = {
     "yond_pack_conv_split_weight_f32": [vp, i32, i32, i32, i32, i32, vp],
     "yond_gemm_k1_stationary_supported": [C.POINTER(YondConvDesc)],
     "yond_conv_s2_tall_supported": [C.POINTER(YondConvDesc)],
+    "yond_conv_split_variant": [C.POINTER(YondConvDesc)],
+    "yond_conv_split_variant_name": [i32],
     "yond_pack_conv_split_weight_dev_f32": [vp, i32, i32, i32, i32, i32, vp, vp, vp],
     "yond_pack_conv_split_weights_batch_dev_f32": [vp, vp, i32, vp, sz, vp, vp],
     "yond_conv_in_f32": [vp, vp, i32, i32, i32, i32, vp, vp, f32, vp, i32, vp],
@@ -191,7 +193,7 @@ def load():
     for name, args in PROTOTYPES.items():
         fn = getattr(lib, name)
         fn.argtypes = args
-        fn.restype = C.c_size_t if name in _SIZE_T_RET else C.c_int
+        fn.restype = C.c_size_t if name in _SIZE_T_RET else C.c_char_p if name == "yond_conv_split_variant_name" else C.c_int
     if lib.yond_abi_version() != ABI_VERSION:
         raise YondHipError(f"{LIB_PATH} has ABI version {lib.yond_abi_version()}, this package binds version {ABI_VERSION} "
                            "(YondConvDesc layout): rebuild with `python -c 'import __graft_entry__ as g; g.build()'`")

@@ -1274,6 +1274,17 @@ __global__ __launch_bounds__(512, 1) void conv_split_kernel(const YondConvDesc d
     }
 }
 
+// ---- tile counts of a launch: the dispatcher's heuristics (conv_split.hip) and the grid below count with the same expressions
+// tiles of th rows x 32 pixels x tn channels over the batch
+inline long long split_tiles(const YondConvDesc& d, int th, int tn) { return (long long)(d.Cout / tn) * ((d.Wo + 31) / 32) * ((d.Ho + th - 1) / th) * d.N; }
+// ... of a folded launch: the sub-tiles (th rows x 32 / f columns) are numbered through the whole batch and taken f at a time
+inline long long split_fold_tiles(const YondConvDesc& d, int th, int tn, int f) {
+    const long long subs = (long long)d.N * ((d.Ho + th - 1) / th) * ((d.Wo + 32 / f - 1) / (32 / f));
+    return (long long)(d.Cout / tn) * ((subs + f - 1) / f);
+}
+// rounds in which the 256 persistent workgroups walk that many tiles
+inline long long split_rounds(long long tiles) { return (tiles + 255) / 256; }
+
 template <int STRIDE, int TH, int TN, int MW, int PARTS, int NWB, bool PRE, bool O4 = false, bool K1 = false, int ISP = 0, bool OSP = false, bool S2 = false, bool D2 = false, int FOLD = 0>
 int launch_split(const YondConvDesc& d, hipStream_t st) {
     using C = SplitCfg<STRIDE, TH, TN, MW, PARTS, NWB, K1, FOLD>;
@@ -1285,9 +1296,9 @@ int launch_split(const YondConvDesc& d, hipStream_t st) {
         if (e != hipSuccess) return (int)e;
         attr_set = true;
     }
-    constexpr int FSWL = FOLD ? 32 / FOLD : 32;
-    const long long total = FOLD ? (long long)(d.Cout / TN) * (((long long)d.N * ((d.Ho + TH - 1) / TH) * ((d.Wo + FSWL - 1) / FSWL) + FOLD - 1) / (FOLD ? FOLD : 1))
-                                 : (long long)(d.Cout / TN) * ((d.Wo + 31) / 32) * ((d.Ho + TH - 1) / TH) * d.N;
+    long long total;
+    if constexpr (FOLD != 0) total = split_fold_tiles(d, TH, TN, FOLD);
+    else total = split_tiles(d, TH, TN);
     if (total > 0x7fffffffLL) return YOND_EUNSUPPORTED;
     const int gmax = (int)yond_exp_long("YOND_SPLIT_GRID", 256);  // (experiment builds: fewer workgroups than CUs, leaving CUs to a side stream's kernels)
     const int grid = total < gmax ? (int)total : gmax;            // one persistent workgroup per CU
@@ -1297,87 +1308,140 @@ int launch_split(const YondConvDesc& d, hipStream_t st) {
 }
 
 
-// ---- the instantiations, grouped into translation units that compile in parallel (conv_split_*.hip); the dispatcher
-// (conv_split.hip) sees them as extern templates.  X(STRIDE, TH, TN, MW, PARTS, NWB, PRE, O4, K1, ISP, OSP)
-#define SPLIT_GROUP_K1S2(X)                                                                             \
-    X(1, 8, 32, 1, 2, 3, false, false, true, false, false) X(1, 8, 64, 2, 2, 3, false, false, true, false, false) \
-    X(2, 4, 64, 1, 2, 2, false, false, false, false, false) X(2, 4, 64, 1, 1, 2, false, false, false, false, false)
-#define SPLIT_GROUP_S1_64(X)                                                                            \
-    X(1, 12, 64, 3, 2, 2, true, false, false, false, false) X(1, 12, 64, 3, 2, 2, false, false, false, false, false) \
-    X(1, 8, 64, 2, 2, 3, true, false, false, false, false) X(1, 8, 64, 2, 2, 3, false, false, false, false, false)
-#define SPLIT_GROUP_S1_32(X)                                                                            \
-    X(1, 16, 32, 2, 2, 3, true, true, false, false, false) X(1, 16, 32, 2, 2, 3, false, true, false, false, false) \
-    X(1, 16, 32, 2, 2, 3, true, false, false, false, false) X(1, 16, 32, 2, 2, 3, false, false, false, false, false)
-#define SPLIT_GROUP_HALF(X)                                                                             \
-    X(1, 8, 64, 2, 1, 3, true, false, false, false, false) X(1, 8, 64, 2, 1, 3, false, false, false, false, false) \
-    X(1, 16, 32, 2, 1, 3, true, false, false, false, false) X(1, 16, 32, 2, 1, 3, false, false, false, false, false)
+// ---- the variants: ONE table.  Everything that must agree on it is generated from it at the end of this file -- the enumeration SplitVariant,
+// the instantiations (grouped into translation units that compile in parallel, conv_split_*.hip), the extern template declarations, the switch
+// that launches an enumerator and the table of names (conv_split.hip) -- so a variant the dispatcher can name is one that is built.
+//   X(NAME, STRIDE, TH, TN, MW, PARTS, NWB, PRE, O4, K1, ISP, OSP, S2, D2, FOLD)
+//   STRIDE 1 / 2; a tile is TH rows x 32 pixels x TN channels; MW output rows per wave; PARTS 2: split operands (h, l), 1: h only; NWB weight buffers
+//   in LDS; PRE SiLU applied while staging; O4 the fused 32 -> 4 output projection; K1 the decoder's pixel-shuffle GEMM; ISP input staging: 0 a
+//   float32 tensor through registers (split there), 1 split planes by LDS-DMA, 2 split planes through registers; OSP split-plane store; S2 two
+//   sub-positions per 64-wide tile (K1); D2 a second output, SiLU(value) in split planes; FOLD 0, or 2 / 4 sub-tiles per MFMA row (images at
+//   most 16 / 8 pixels wide).
+//   NAME = <s1 | s2 | k1: stride, or the decoder GEMM>_<TH>x<TN>_<split | h: operands>_<f32 | dma | reg: ISP 0 / 1 / 2>_<f32 | sp: float32 tensor
+//   or split-plane store>, then what applies of _o4 _sub2 _d2 _f2 / _f4 (FOLD) _wres (two weight buffers, on which the weights of a 32 -> 32 layer
+//   stay resident) and, last, _pre: the two PRE forms of a layer share their stem.  MW follows from (STRIDE, TH, TN), NWB from those and _wres.
+#define SPLIT_GROUP_K1S2(X)                                                                              \
+    X(k1_8x32_split_f32_f32,          1, 8, 32, 1, 2, 3, false, false, true, 0, false, false, false, 0)  \
+    X(k1_8x64_split_f32_f32,          1, 8, 64, 2, 2, 3, false, false, true, 0, false, false, false, 0)  \
+    X(s2_4x64_split_f32_f32,          2, 4, 64, 1, 2, 2, false, false, false, 0, false, false, false, 0) \
+    X(s2_4x64_h_f32_f32,              2, 4, 64, 1, 1, 2, false, false, false, 0, false, false, false, 0)
+#define SPLIT_GROUP_S1_64(X)                                                                              \
+    X(s1_12x64_split_f32_f32_pre,     1, 12, 64, 3, 2, 2, true, false, false, 0, false, false, false, 0)  \
+    X(s1_12x64_split_f32_f32,         1, 12, 64, 3, 2, 2, false, false, false, 0, false, false, false, 0) \
+    X(s1_8x64_split_f32_f32_pre,      1, 8, 64, 2, 2, 3, true, false, false, 0, false, false, false, 0)   \
+    X(s1_8x64_split_f32_f32,          1, 8, 64, 2, 2, 3, false, false, false, 0, false, false, false, 0)
+#define SPLIT_GROUP_S1_32(X)                                                                              \
+    X(s1_16x32_split_f32_f32_o4_pre,  1, 16, 32, 2, 2, 3, true, true, false, 0, false, false, false, 0)   \
+    X(s1_16x32_split_f32_f32_o4,      1, 16, 32, 2, 2, 3, false, true, false, 0, false, false, false, 0)  \
+    X(s1_16x32_split_f32_f32_pre,     1, 16, 32, 2, 2, 3, true, false, false, 0, false, false, false, 0)  \
+    X(s1_16x32_split_f32_f32,         1, 16, 32, 2, 2, 3, false, false, false, 0, false, false, false, 0)
+#define SPLIT_GROUP_HALF(X)                                                                               \
+    X(s1_8x64_h_f32_f32_pre,          1, 8, 64, 2, 1, 3, true, false, false, 0, false, false, false, 0)   \
+    X(s1_8x64_h_f32_f32,              1, 8, 64, 2, 1, 3, false, false, false, 0, false, false, false, 0)  \
+    X(s1_16x32_h_f32_f32_pre,         1, 16, 32, 2, 1, 3, true, false, false, 0, false, false, false, 0)  \
+    X(s1_16x32_h_f32_f32,             1, 16, 32, 2, 1, 3, false, false, false, 0, false, false, false, 0)
 // h-only operands (the fp16 path, BASELINE cfg 5) leave ONE accumulator per block: a wave can own two 32-channel blocks in the registers
 // the split form spends on its second accumulator -- 128-channel tiles: every pixel fragment read from LDS serves two blocks, twice the
 // MFMAs per staged input, per weight DMA and per barrier
-#define SPLIT_GROUP_HALF128(X)                                                                          \
-    X(1, 12, 128, 3, 1, 2, true, false, false, false, false) X(1, 12, 128, 3, 1, 2, false, false, false, false, false) \
-    X(1, 8, 128, 2, 1, 3, true, false, false, false, false) X(1, 8, 128, 2, 1, 3, false, false, false, false, false)
+#define SPLIT_GROUP_HALF128(X)                                                                             \
+    X(s1_12x128_h_f32_f32_pre,        1, 12, 128, 3, 1, 2, true, false, false, 0, false, false, false, 0)  \
+    X(s1_12x128_h_f32_f32,            1, 12, 128, 3, 1, 2, false, false, false, 0, false, false, false, 0) \
+    X(s1_8x128_h_f32_f32_pre,         1, 8, 128, 2, 1, 3, true, false, false, 0, false, false, false, 0)   \
+    X(s1_8x128_h_f32_f32,             1, 8, 128, 2, 1, 3, false, false, false, 0, false, false, false, 0)
 // ... and, for the layers with 64 / 32 output channels, taller tiles than the split form's registers allow: 12 rows x 64 channels (three
 // rows per wave) and 32 rows x 32 channels (four rows per wave; its input image is also the first of this path large enough to serve as
 // the transposed epilogue's scratch -- the 16-row form stores from the accumulator layout, 32 cache lines per instruction)
-#define SPLIT_GROUP_HALF_TALL(X)                                                                        \
-    X(1, 12, 64, 3, 1, 2, true, false, false, false, false) X(1, 12, 64, 3, 1, 2, false, false, false, false, false) \
-    X(1, 32, 32, 4, 1, 2, true, false, false, false, false) X(1, 32, 32, 4, 1, 2, false, false, false, false, false)
-#define SPLIT_GROUP_OSP(X)                                                                              \
-    X(1, 12, 64, 3, 2, 2, true, false, false, false, true) X(1, 12, 64, 3, 2, 2, false, false, false, false, true) \
-    X(1, 8, 64, 2, 2, 3, true, false, false, false, true) X(1, 8, 64, 2, 2, 3, false, false, false, false, true) \
-    X(1, 16, 32, 2, 2, 3, true, false, false, false, true) X(1, 16, 32, 2, 2, 3, false, false, false, false, true)
-#define SPLIT_GROUP_ISP(X)                                                                              \
-    X(1, 12, 64, 3, 2, 2, false, false, false, true, false) X(1, 8, 64, 2, 2, 3, false, false, false, true, false) \
-    X(1, 16, 32, 2, 2, 3, false, true, false, true, false) X(1, 16, 32, 2, 2, 3, false, false, false, true, false)
-#define SPLIT_GROUP_ISP_OSP(X)                                                                          \
-    X(1, 12, 64, 3, 2, 2, false, false, false, true, true) X(1, 8, 64, 2, 2, 3, false, false, false, true, true) \
-    X(1, 16, 32, 2, 2, 3, false, false, false, true, true)
-#define SPLIT_GROUP_ISP_K1S2(X)                                                                         \
-    X(1, 8, 32, 1, 2, 3, false, false, true, 2, false) X(1, 8, 64, 2, 2, 3, false, false, true, 2, false) \
-    X(2, 4, 64, 1, 2, 2, false, false, false, 2, false)
-#define SPLIT_GROUP_K1_SUB2(X) X(1, 8, 64, 2, 2, 3, false, false, true, 2, false, true)
+#define SPLIT_GROUP_HALF_TALL(X)                                                                          \
+    X(s1_12x64_h_f32_f32_pre,         1, 12, 64, 3, 1, 2, true, false, false, 0, false, false, false, 0)  \
+    X(s1_12x64_h_f32_f32,             1, 12, 64, 3, 1, 2, false, false, false, 0, false, false, false, 0) \
+    X(s1_32x32_h_f32_f32_pre,         1, 32, 32, 4, 1, 2, true, false, false, 0, false, false, false, 0)  \
+    X(s1_32x32_h_f32_f32,             1, 32, 32, 4, 1, 2, false, false, false, 0, false, false, false, 0)
+#define SPLIT_GROUP_OSP(X)                                                                                \
+    X(s1_12x64_split_f32_sp_pre,      1, 12, 64, 3, 2, 2, true, false, false, 0, true, false, false, 0)   \
+    X(s1_12x64_split_f32_sp,          1, 12, 64, 3, 2, 2, false, false, false, 0, true, false, false, 0)  \
+    X(s1_8x64_split_f32_sp_pre,       1, 8, 64, 2, 2, 3, true, false, false, 0, true, false, false, 0)    \
+    X(s1_8x64_split_f32_sp,           1, 8, 64, 2, 2, 3, false, false, false, 0, true, false, false, 0)   \
+    X(s1_16x32_split_f32_sp_pre,      1, 16, 32, 2, 2, 3, true, false, false, 0, true, false, false, 0)   \
+    X(s1_16x32_split_f32_sp,          1, 16, 32, 2, 2, 3, false, false, false, 0, true, false, false, 0)
+#define SPLIT_GROUP_ISP(X)                                                                                \
+    X(s1_12x64_split_dma_f32,         1, 12, 64, 3, 2, 2, false, false, false, 1, false, false, false, 0) \
+    X(s1_8x64_split_dma_f32,          1, 8, 64, 2, 2, 3, false, false, false, 1, false, false, false, 0)  \
+    X(s1_16x32_split_dma_f32_o4,      1, 16, 32, 2, 2, 3, false, true, false, 1, false, false, false, 0)  \
+    X(s1_16x32_split_dma_f32,         1, 16, 32, 2, 2, 3, false, false, false, 1, false, false, false, 0)
+#define SPLIT_GROUP_ISP_OSP(X)                                                                            \
+    X(s1_12x64_split_dma_sp,          1, 12, 64, 3, 2, 2, false, false, false, 1, true, false, false, 0)  \
+    X(s1_8x64_split_dma_sp,           1, 8, 64, 2, 2, 3, false, false, false, 1, true, false, false, 0)   \
+    X(s1_16x32_split_dma_sp,          1, 16, 32, 2, 2, 3, false, false, false, 1, true, false, false, 0)
+#define SPLIT_GROUP_ISP_K1S2(X)                                                                           \
+    X(k1_8x32_split_reg_f32,          1, 8, 32, 1, 2, 3, false, false, true, 2, false, false, false, 0)   \
+    X(k1_8x64_split_reg_f32,          1, 8, 64, 2, 2, 3, false, false, true, 2, false, false, false, 0)   \
+    X(s2_4x64_split_reg_f32,          2, 4, 64, 1, 2, 2, false, false, false, 2, false, false, false, 0)
+#define SPLIT_GROUP_K1_SUB2(X)                                                                            \
+    X(k1_8x64_split_reg_f32_sub2,     1, 8, 64, 2, 2, 3, false, false, true, 2, false, true, false, 0)
 // folded tiles (images at most 16 pixels wide): the 8-row kernel of the split-plane data flow with two 16-column sub-tiles per MFMA row
-#define SPLIT_GROUP_FOLD(X)                                                                             \
-    X(1, 4, 64, 1, 2, 3, false, false, false, true, true, false, false, 2) X(1, 4, 64, 1, 2, 3, true, false, false, false, true, false, false, 2)         \
-    X(1, 4, 64, 1, 2, 3, false, false, false, true, true, false, false, 4) X(1, 4, 64, 1, 2, 3, true, false, false, false, true, false, false, 4)
-// ... the decoder GEMMs (no halo: the sub-tiles lie side by side as the columns of one tile do)
+#define SPLIT_GROUP_FOLD(X)                                                                               \
+    X(s1_4x64_split_dma_sp_f2,        1, 4, 64, 1, 2, 3, false, false, false, 1, true, false, false, 2)   \
+    X(s1_4x64_split_f32_sp_f2_pre,    1, 4, 64, 1, 2, 3, true, false, false, 0, true, false, false, 2)    \
+    X(s1_4x64_split_dma_sp_f4,        1, 4, 64, 1, 2, 3, false, false, false, 1, true, false, false, 4)   \
+    X(s1_4x64_split_f32_sp_f4_pre,    1, 4, 64, 1, 2, 3, true, false, false, 0, true, false, false, 4)
 // ... the plain [N][H][W][C] layer (training's forward and data-gradient convolutions, UNetSeeInDark's deep stages)
-#define SPLIT_GROUP_FOLD_NHWC(X) X(1, 4, 64, 1, 2, 3, false, false, false, 0, false, false, false, 2) X(1, 4, 64, 1, 2, 3, false, false, false, 0, false, false, false, 4)
+#define SPLIT_GROUP_FOLD_NHWC(X)                                                                          \
+    X(s1_4x64_split_f32_f32_f2,       1, 4, 64, 1, 2, 3, false, false, false, 0, false, false, false, 2)  \
+    X(s1_4x64_split_f32_f32_f4,       1, 4, 64, 1, 2, 3, false, false, false, 0, false, false, false, 4)
 // the decoder GEMM that also stores SiLU(value) in split planes (YondConvDesc.dst2: the next block's conv1 then stages by LDS-DMA alone)
-#define SPLIT_GROUP_K1_D2(X) X(1, 8, 64, 2, 2, 3, false, false, true, 2, false, false, true)
-#define SPLIT_GROUP_FOLD_K1(X) X(1, 8, 64, 2, 2, 3, false, false, true, 2, false, false, false, 2) X(1, 8, 64, 2, 2, 3, false, false, true, 2, false, false, false, 4)
-// ... and the stride-2 layers of the flow (split planes in, planes of 4 channels out, with and without the second, split-plane output)
-#define SPLIT_GROUP_FOLD_S2(X)                                                                          \
-    X(2, 4, 64, 1, 2, 2, false, false, false, 2, false, false, true, 2) X(2, 4, 64, 1, 2, 2, false, false, false, 2, false, false, false, 2)            \
-    X(2, 4, 64, 1, 2, 2, false, false, false, 2, false, false, true, 4) X(2, 4, 64, 1, 2, 2, false, false, false, 2, false, false, false, 4)            \
-    X(2, 4, 64, 1, 2, 2, false, false, false, 0, false, false, false, 2) X(2, 4, 64, 1, 2, 2, false, false, false, 0, false, false, false, 4)
-#define SPLIT_GROUP_D2(X) X(2, 4, 64, 1, 2, 2, false, false, false, 2, false, false, true)
-#define SPLIT_GROUP_WRES(X)                                                                             \
-    X(1, 16, 32, 2, 2, 2, true, false, false, false, true) X(1, 16, 32, 2, 2, 2, false, false, false, true, true) \
-    X(1, 16, 32, 2, 2, 2, false, true, false, true, false)
+#define SPLIT_GROUP_K1_D2(X)                                                                              \
+    X(k1_8x64_split_reg_f32_d2,       1, 8, 64, 2, 2, 3, false, false, true, 2, false, false, true, 0)
+// ... the folded decoder GEMMs (no halo: the sub-tiles lie side by side as the columns of one tile do)
+#define SPLIT_GROUP_FOLD_K1(X)                                                                            \
+    X(k1_8x64_split_reg_f32_f2,       1, 8, 64, 2, 2, 3, false, false, true, 2, false, false, false, 2)   \
+    X(k1_8x64_split_reg_f32_f4,       1, 8, 64, 2, 2, 3, false, false, true, 2, false, false, false, 4)
+// ... and the folded stride-2 layers: of the flow (split planes in, planes of 4 channels out, with and without the second, split-plane output)
+// and of the [N][H][W][C] path (training's forward)
+#define SPLIT_GROUP_FOLD_S2(X)                                                                            \
+    X(s2_4x64_split_reg_f32_d2_f2,    2, 4, 64, 1, 2, 2, false, false, false, 2, false, false, true, 2)   \
+    X(s2_4x64_split_reg_f32_f2,       2, 4, 64, 1, 2, 2, false, false, false, 2, false, false, false, 2)  \
+    X(s2_4x64_split_reg_f32_d2_f4,    2, 4, 64, 1, 2, 2, false, false, false, 2, false, false, true, 4)   \
+    X(s2_4x64_split_reg_f32_f4,       2, 4, 64, 1, 2, 2, false, false, false, 2, false, false, false, 4)  \
+    X(s2_4x64_split_f32_f32_f2,       2, 4, 64, 1, 2, 2, false, false, false, 0, false, false, false, 2)  \
+    X(s2_4x64_split_f32_f32_f4,       2, 4, 64, 1, 2, 2, false, false, false, 0, false, false, false, 4)
+#define SPLIT_GROUP_D2(X)                                                                                 \
+    X(s2_4x64_split_reg_f32_d2,       2, 4, 64, 1, 2, 2, false, false, false, 2, false, false, true, 0)
+// 32 -> 32 channels: two weight slices in all -- on two buffers they stay resident in LDS (the kernel's `wres`)
+#define SPLIT_GROUP_WRES(X)                                                                               \
+    X(s1_16x32_split_f32_sp_wres_pre, 1, 16, 32, 2, 2, 2, true, false, false, 0, true, false, false, 0)   \
+    X(s1_16x32_split_dma_sp_wres,     1, 16, 32, 2, 2, 2, false, false, false, 1, true, false, false, 0)  \
+    X(s1_16x32_split_dma_f32_o4_wres, 1, 16, 32, 2, 2, 2, false, true, false, 1, false, false, false, 0)
 // ---- the split-plane data flow on H-ONLY planes (PARTS 1: the fp16 path, BASELINE cfg 5): block-internal and block-output tensors travel as
 // 2-byte halves [n][C/16][channel half][H*W (+ zero pad)] x 16-byte units
 // conv1 from the float32 block input (planes of 4 channels), SiLU in its staging, h-only store
-#define SPLIT_GROUP_H_OSP(X)                                                                            \
-    X(1, 12, 64, 3, 1, 2, true, false, false, false, true) X(1, 8, 64, 2, 1, 3, true, false, false, false, true) \
-    X(1, 16, 32, 2, 1, 3, true, false, false, false, true)
+#define SPLIT_GROUP_H_OSP(X)                                                                              \
+    X(s1_12x64_h_f32_sp_pre,          1, 12, 64, 3, 1, 2, true, false, false, 0, true, false, false, 0)   \
+    X(s1_8x64_h_f32_sp_pre,           1, 8, 64, 2, 1, 3, true, false, false, 0, true, false, false, 0)    \
+    X(s1_16x32_h_f32_sp_pre,          1, 16, 32, 2, 1, 3, true, false, false, 0, true, false, false, 0)
 // conv2 (h-only planes in by LDS-DMA, FiLM + float32 residual in planes of 4, h-only store) and conv1 of the levels whose producer stored SiLU(x)
-#define SPLIT_GROUP_H_ISP_OSP(X)                                                                        \
-    X(1, 12, 64, 3, 1, 2, false, false, false, true, true) X(1, 8, 64, 2, 1, 3, false, false, false, true, true) \
-    X(1, 16, 32, 2, 1, 3, false, false, false, true, true)
+#define SPLIT_GROUP_H_ISP_OSP(X)                                                                          \
+    X(s1_12x64_h_dma_sp,              1, 12, 64, 3, 1, 2, false, false, false, 1, true, false, false, 0)  \
+    X(s1_8x64_h_dma_sp,               1, 8, 64, 2, 1, 3, false, false, false, 1, true, false, false, 0)   \
+    X(s1_16x32_h_dma_sp,              1, 16, 32, 2, 1, 3, false, false, false, 1, true, false, false, 0)
 // the last convolution with the fused output projection
-#define SPLIT_GROUP_H_ISP_O4(X) X(1, 16, 32, 2, 1, 3, false, true, false, true, false)
+#define SPLIT_GROUP_H_ISP_O4(X)                                                                           \
+    X(s1_16x32_h_dma_f32_o4,          1, 16, 32, 2, 1, 3, false, true, false, 1, false, false, false, 0)
 // stride 2 and the decoder GEMMs: h-only planes through the register sets, planes of 4 channels (float32) out; with the second (h-only) output
-#define SPLIT_GROUP_H_K1S2(X)                                                                           \
-    X(1, 8, 32, 1, 1, 3, false, false, true, 2, false) X(1, 8, 64, 2, 1, 3, false, false, true, 2, false) \
-    X(2, 4, 64, 1, 1, 2, false, false, false, 2, false)
-#define SPLIT_GROUP_H_D2(X) X(2, 4, 64, 1, 1, 2, false, false, false, 2, false, false, true) X(1, 8, 64, 2, 1, 3, false, false, true, 2, false, false, true)
-#define SPLIT_GROUP_H_SUB2(X) X(1, 8, 64, 2, 1, 3, false, false, true, 2, false, true)
+#define SPLIT_GROUP_H_K1S2(X)                                                                             \
+    X(k1_8x32_h_reg_f32,              1, 8, 32, 1, 1, 3, false, false, true, 2, false, false, false, 0)   \
+    X(k1_8x64_h_reg_f32,              1, 8, 64, 2, 1, 3, false, false, true, 2, false, false, false, 0)   \
+    X(s2_4x64_h_reg_f32,              2, 4, 64, 1, 1, 2, false, false, false, 2, false, false, false, 0)
+#define SPLIT_GROUP_H_D2(X)                                                                               \
+    X(s2_4x64_h_reg_f32_d2,           2, 4, 64, 1, 1, 2, false, false, false, 2, false, false, true, 0)   \
+    X(k1_8x64_h_reg_f32_d2,           1, 8, 64, 2, 1, 3, false, false, true, 2, false, false, true, 0)
+#define SPLIT_GROUP_H_SUB2(X)                                                                             \
+    X(k1_8x64_h_reg_f32_sub2,         1, 8, 64, 2, 1, 3, false, false, true, 2, false, true, false, 0)
 // ... and 128-channel tiles for the flow's 3x3 layers with >= 128 output channels (one accumulator per block: a wave owns two blocks, as in HALF128)
 // (8-row tiles: the 12-row forms of these two spill 33 / 45 registers)
-#define SPLIT_GROUP_H128_OSP(X) X(1, 8, 128, 2, 1, 3, true, false, false, false, true)
-#define SPLIT_GROUP_H128_ISP_OSP(X) X(1, 8, 128, 2, 1, 3, false, false, false, true, true)
+#define SPLIT_GROUP_H128_OSP(X)                                                                           \
+    X(s1_8x128_h_f32_sp_pre,          1, 8, 128, 2, 1, 3, true, false, false, 0, true, false, false, 0)
+#define SPLIT_GROUP_H128_ISP_OSP(X)                                                                       \
+    X(s1_8x128_h_dma_sp,              1, 8, 128, 2, 1, 3, false, false, false, 1, true, false, false, 0)
 // (resident weights for the 32 -> 32 layers, as SPLIT_GROUP_WRES, measured on this path in round 6: no gain -- its level 0 is bound by HBM bytes and the
 // SiLU arithmetic, not by the weight DMA -- and not built)
 // ... and the flow's stride-2 layers on 8-row tiles, two output rows per wave, 64 or 128 channels: with h-only operands a fragment read from LDS feeds
@@ -1385,19 +1449,35 @@ int launch_split(const YondConvDesc& d, hipStream_t st) {
 // LDS-read bound (in-kernel stamps, profiles/r06_experiments).  Two rows per wave share every weight fragment and 1 of 6 pixel-row fragments
 // (1.33 KiB per MFMA), two channel blocks per wave share every pixel fragment (0.92); the h-only planes leave the LDS for the 17-row input image
 // (the 128-channel form with the second output spills 42 registers: not built -- those layers take the 64-channel form)
-#define SPLIT_GROUP_H_S2_TALL(X)                                                                        \
-    X(2, 8, 64, 2, 1, 2, false, false, false, 2, false) X(2, 8, 128, 2, 1, 2, false, false, false, 2, false) \
-    X(2, 8, 64, 2, 1, 2, false, false, false, 2, false, false, true)
+#define SPLIT_GROUP_H_S2_TALL(X)                                                                          \
+    X(s2_8x64_h_reg_f32,              2, 8, 64, 2, 1, 2, false, false, false, 2, false, false, false, 0)  \
+    X(s2_8x128_h_reg_f32,             2, 8, 128, 2, 1, 2, false, false, false, 2, false, false, false, 0) \
+    X(s2_8x64_h_reg_f32_d2,           2, 8, 64, 2, 1, 2, false, false, false, 2, false, false, true, 0)
 // ... and its decoder GEMMs: 16-row tiles (four rows per wave share every weight fragment), 128 GEMM columns where an output pixel has >= 128 channels
 // (two column blocks per wave share every pixel fragment): 1.5 KiB of LDS fragments per MFMA (8 rows x 64 columns) -> 1.25 (16 x 64) / 1.0 (8 x 128)
 // (16 rows x 128 columns spills 52 registers: not built)
-#define SPLIT_GROUP_H_K1_TALL(X) X(1, 16, 64, 4, 1, 2, false, false, true, 2, false) X(1, 8, 128, 2, 1, 3, false, false, true, 2, false)
+#define SPLIT_GROUP_H_K1_TALL(X)                                                                          \
+    X(k1_16x64_h_reg_f32,             1, 16, 64, 4, 1, 2, false, false, true, 2, false, false, false, 0)  \
+    X(k1_8x128_h_reg_f32,             1, 8, 128, 2, 1, 3, false, false, true, 2, false, false, false, 0)
 // ... and four rows per wave for its 32- and 64-channel 3x3 layers (every weight fragment serves four rows: 1.17 -> 0.75 and 0.89 -> 0.75 KiB of LDS
 // fragments per MFMA; the 32-row forms with register-staged input / the output projection spill 39 / 8 registers: not built)
-#define SPLIT_GROUP_H_TALL4(X)                                                                          \
-    X(1, 32, 32, 4, 1, 2, false, false, false, true, true)                                               \
-    X(1, 16, 64, 4, 1, 2, true, false, false, false, true) X(1, 16, 64, 4, 1, 2, false, false, false, true, true)
+#define SPLIT_GROUP_H_TALL4(X)                                                                            \
+    X(s1_32x32_h_dma_sp,              1, 32, 32, 4, 1, 2, false, false, false, 1, true, false, false, 0)  \
+    X(s1_16x64_h_f32_sp_pre,          1, 16, 64, 4, 1, 2, true, false, false, 0, true, false, false, 0)   \
+    X(s1_16x64_h_dma_sp,              1, 16, 64, 4, 1, 2, false, false, false, 1, true, false, false, 0)
 // (measured slower and retired, source in git history: the stride-2 layers with one wave per SIMD or with multiplying / moving wave roles -- profiles/r06_experiments/README.md,
 // s2_*_ab.txt -- and level 0's half-size workgroups, two per CU -- profiles/r06_experiments/README.md, DESIGN.md sections 0 and 8)
-#define SPLIT_INSTANTIATE(...) template int launch_split<__VA_ARGS__>(const YondConvDesc&, hipStream_t);
-#define SPLIT_EXTERN(...) extern template int launch_split<__VA_ARGS__>(const YondConvDesc&, hipStream_t);
+
+// every group: one that is missing here has no enumerators, so the dispatcher cannot name its variants; one that no translation unit instantiates fails the link
+#define SPLIT_VARIANTS(X)                                                                                                                 \
+    SPLIT_GROUP_K1S2(X) SPLIT_GROUP_S1_64(X) SPLIT_GROUP_S1_32(X) SPLIT_GROUP_HALF(X) SPLIT_GROUP_HALF128(X) SPLIT_GROUP_HALF_TALL(X)      \
+    SPLIT_GROUP_OSP(X) SPLIT_GROUP_ISP(X) SPLIT_GROUP_ISP_OSP(X) SPLIT_GROUP_ISP_K1S2(X) SPLIT_GROUP_K1_SUB2(X) SPLIT_GROUP_FOLD(X)        \
+    SPLIT_GROUP_FOLD_NHWC(X) SPLIT_GROUP_K1_D2(X) SPLIT_GROUP_FOLD_K1(X) SPLIT_GROUP_FOLD_S2(X) SPLIT_GROUP_D2(X) SPLIT_GROUP_WRES(X)      \
+    SPLIT_GROUP_H_OSP(X) SPLIT_GROUP_H_ISP_OSP(X) SPLIT_GROUP_H_ISP_O4(X) SPLIT_GROUP_H_K1S2(X) SPLIT_GROUP_H_D2(X) SPLIT_GROUP_H_SUB2(X)  \
+    SPLIT_GROUP_H128_OSP(X) SPLIT_GROUP_H128_ISP_OSP(X) SPLIT_GROUP_H_S2_TALL(X) SPLIT_GROUP_H_K1_TALL(X) SPLIT_GROUP_H_TALL4(X)
+#define SPLIT_ENUM(NAME, ...) SV_##NAME,
+#define SPLIT_NAME(NAME, ...) #NAME,
+#define SPLIT_INSTANTIATE(NAME, ...) template int launch_split<__VA_ARGS__>(const YondConvDesc&, hipStream_t);
+#define SPLIT_EXTERN(NAME, ...) extern template int launch_split<__VA_ARGS__>(const YondConvDesc&, hipStream_t);
+#define SPLIT_LAUNCH_CASE(NAME, ...) case SV_##NAME: return launch_split<__VA_ARGS__>(d, st);
+enum SplitVariant : int { SPLIT_VARIANTS(SPLIT_ENUM) SV_COUNT };

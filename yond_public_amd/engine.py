@@ -411,6 +411,8 @@ class DenoiserPlan:
             # (h-only operands: 128-channel tiles for plain tensors only; the decoder GEMM only inside the split-plane flow)
             # (the stride-2 layers of the h-only flow: 128-channel tiles where 8-row tiles fill the 256 workgroups and there is no second output --
             #  that instantiation spills)
+            # (this count repeats the dispatcher's rule -- csrc/conv_split.hip, split_s2_h_tall, which refuses the 128-channel form below it -- because
+            #  the weights are packed here, before there is a descriptor to ask yond_conv_split_variant with: keep the two in step)
             ws2 = (HALF_S2_TN128 and algo == 'half' and pc.stride == 2 and in_fmt == 1 and out_fmt == 2 and dst2 is None
                    and (pc.gemm_n // 128) * ((d.Wo + 31) // 32) * ((d.Ho + 7) // 8) * N >= 256)
             ws2 = ws2 or (HALF_K1_TN128 and algo == 'half' and pc.ksize == 1 and in_fmt == 1 and dst2 is None)
