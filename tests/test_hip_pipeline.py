@@ -402,6 +402,34 @@ def test_denoise_stream_iter_matches_iterdenoise(weights):
             assert float((x - y).abs().max()) <= 5e-6                    # (two IterDenoise runs differ by up to 1e-6 themselves: atomics in the moment sums)
 
 
+def test_denoise_stream_iter_closed_early_rejoins_the_callers_stream():
+    """The consumer takes one result of four frames and closes the generator: frames 1 to 3 are still queued on the side stream and the second
+    passes' lane.  The driver leaves the plan on lane 0 and the caller's stream behind its lanes, the device drains, and the next call on the
+    caller's stream -- IterDenoise of frame 0 -- gives what the stream yielded for it."""
+    import yond_public_amd.pipeline as P
+    import yond_public_amd.archs as A
+    import yond_public_amd.synthetic as S
+    dev = torch.device('cuda:0')
+    arch = dict(name='GuidedResUnet', in_nc=4, out_nc=4, nf=32, nframes=1, res=True, norm=True, guided=True)
+    net = A.GuidedResUnet(dict(arch))
+    net.load_state_dict(S.denoising_state_dict(net, 0))
+    net = net.to(dev).eval()
+    pipe = {'k': 29, 'vst_type': 'exact', 'bias_corr': 'pre', 'iter': 'iter', 'max_iter': 1, 'full_dn': True}
+    frames = [torch.from_numpy(S.synth_noisy(128, 192, 3.0 + i, 5.0 + 2 * i, 10 + i)[0]).to(dev) for i in range(4)]
+    assert P.STREAM_ITER and P.STREAM_LANES == 2 and P.stream_applies(pipe)
+    plan = P._plan_of(net, dev)
+    gen = P.denoise_stream(iter(frames), net, arch, pipe)
+    first = next(gen)
+    gen.close()
+    assert plan.lane == 0
+    torch.cuda.synchronize()
+    want = P.IterDenoise(frames[0], net, arch, pipe)
+    assert len(first['raw_dns']) == len(want['raw_dns']) and len(first['regs']) == len(want['regs'])
+    assert np.allclose(np.asarray(first['regs'], np.float64), np.asarray(want['regs'], np.float64), rtol=1e-9, atol=0)
+    for x, y in zip(first['raw_dns'], want['raw_dns']):
+        assert float((x - y).abs().max()) <= 5e-6                        # (the file's bound for a stream against IterDenoise)
+
+
 def test_cfg4_unet_batch8_full_size():
     """BASELINE cfg 4 at its real shape: UNetSeeInDark, batch 8 of 3000 x 4000 frames (packed, padded 1504 x 2016) in ONE
     forward; every item equals its batch-1 forward bit for bit (no cross-item coupling, deterministic tile arithmetic)."""

@@ -34,6 +34,8 @@ def _np_ptr(a):
 
 
 FILM_MAX_C = 1024                   # widest block of yond_film_f32 (YondFilmDesc.C, include/yond_hip.h)
+STATUS_WORDS = 12                   # range-guard words of a plan (`status`): 0-2 the pipeline wrappers, 3 the plugin surface, 4-11 the stream drivers'
+                                    # rings (pipeline._guard_slot refuses a ring that does not fit)
 
 
 # 3x3 stride-1 layers: 1 = Winograd F(2x2,3x3) wherever the kernel supports the shape (measured 1.45-1.5x over the direct
@@ -307,8 +309,7 @@ class DenoiserPlan:
         self.lib = L.load()
         self.dev = torch.device(device)
         self.prof = None                           # list -> record (kernel tag, flops, start, end) HIP events per conv launch
-        self.status = torch.zeros(12, dtype=torch.int32, device=self.dev)    # range-guard words of the half-precision paths (0-2: pipeline wrappers, 3: the
-                                                                             # plugin surface, 4-11: the two-stream 'iter' driver's ring)
+        self.status = torch.zeros(STATUS_WORDS, dtype=torch.int32, device=self.dev)    # range-guard words of the half-precision paths
         self.status_slot = 0
         self.strict = False                        # True: every convolution on the fp32-input MFMA kernels (guard fallback)
         self.precision = precision                 # 'fp16': MFMA convolutions on the fp16 matrix path (cfg 5)

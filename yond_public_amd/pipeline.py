@@ -10,6 +10,7 @@ Images are float32 torch tensors on a ROCm device (NumPy arrays are uploaded).  
 control flow and O(20)-element arithmetic (threshold score, 2x2 normal equations, LUT knot grid); every
 pass over pixels is a kernel launch through the C ABI of libyond_hip.so.
 """
+import contextlib
 import ctypes as C
 import math
 
@@ -19,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .engine import STATUS_WORDS
 
 NBINS = 1024
 
@@ -760,9 +762,11 @@ class _Guard:
     silent inf."""
 
     def __init__(self, plan, slot):
+        if not 0 <= slot < STATUS_WORDS:               # (the kernels write the word at status + 4 * slot)
+            raise L.YondHipError(f"range guard: status word {slot} of {STATUS_WORDS}")
         self.plan, self.slot = plan, slot
         if not hasattr(plan, '_flag_host'):
-            plan._flag_host = torch.zeros(12, dtype=torch.int32).pin_memory()
+            plan._flag_host = torch.zeros(STATUS_WORDS, dtype=torch.int32).pin_memory()
         plan.begin_guard(slot)
 
     def arm(self, rerun):
@@ -1118,6 +1122,92 @@ def _chain_result(buf):
     return reg, (np.float64(v[PRM['gain']]), np.float64(v[PRM['sigma']])), flags, info
 
 
+def _chain_verdict(rounds, reached=None):
+    """What becomes of a frame whose rounds were queued on the device chain.  rounds: per round that ran, (flag word of its parameter block,
+    whether its range guard tripped -- a bool, or a callable asked only when the answer depends on it: _Guard.tripped waits for the forward).
+    'host': a round took a branch the chain leaves to the host-side chain; 'round1': round 2 ended at beta1 < 0 (YOND_SIDD.py:445-447) and the
+    frame keeps round 1 alone; 'both': every round that ran counts.  An aborted round 2 computed nothing further, so its PRM_BAD_ESTIMATE and
+    its guard count only when it was not aborted.  reached(r) is called once round r's estimate stands, as IterDenoise logs it: round 1's after
+    all of its checks, round 2's before its abort, estimate and guard checks."""
+    unusable = PRM_NO_FLAT_AREA | PRM_LUT_CAPACITY
+
+    def tripped(t):
+        return bool(t() if callable(t) else t)
+
+    fl1, trip1 = rounds[0]
+    if fl1 & (unusable | PRM_BAD_ESTIMATE) or tripped(trip1):
+        return 'host'
+    if reached:
+        reached(0)
+    if len(rounds) == 1:
+        return 'both'
+    fl2, trip2 = rounds[1]
+    if fl2 & unusable:
+        return 'host'
+    if reached:
+        reached(1)
+    if fl2 & PRM_ROUND_ABORTED:
+        return 'round1'
+    if fl2 & PRM_BAD_ESTIMATE or tripped(trip2):
+        return 'host'
+    return 'both'
+
+
+def _chain_answer(verdict, outs, blocks):
+    """The drivers' result for a frame from its rounds' outputs and their _chain_result tuples; None for the verdict 'host'."""
+    if verdict == 'host':
+        return None
+    n = 1 if verdict == 'round1' else len(blocks)
+    return dict(raw_dns=list(outs[:n]), regs=[b[0] for b in blocks[:n]], params=[b[1] for b in blocks[:n]], nle_info=blocks[0][3])
+
+
+def _chain_settle(bufs, outs, guards, log=None, tag=""):
+    """Verdict and answer of one frame whose rounds have finished: bufs / outs / guards per round (a guard: a _Guard, None, or the bool an
+    earlier read of a guard shared with other frames gave)."""
+    blocks = [_chain_result(b) for b in bufs]
+
+    def say(r):
+        reg, par = blocks[r][:2]
+        name, second = (f"Iter {r} Est", "sigma") if r else ("Self Est", "b")
+        log(f"{tag}{name}: K={par[0]:.4f}, {second}={par[1]:.4f} (beta1={reg[0]:.3e}, beta2={reg[1]:.3e})")
+
+    rounds = [(b[2], g.tripped if isinstance(g, _Guard) else bool(g)) for b, g in zip(blocks, guards)]
+    return _chain_answer(_chain_verdict(rounds, say if log else None), outs, blocks)
+
+
+def _host_chain_redo(lr, net, arch, pipe, p):
+    """A frame the device chain handed back: IterDenoise with the chain off (the one place that switches DEVICE_CHAIN)."""
+    global DEVICE_CHAIN
+    DEVICE_CHAIN = False
+    try:
+        return IterDenoise(lr, net, arch, pipe, p=p)
+    finally:
+        DEVICE_CHAIN = True
+
+
+def _guard_slot(k, ring, r=0, per_frame=1):
+    """Status word of round r of frame k in a driver whose ring holds `ring` frames of `per_frame` words each (words 0-3 belong to the
+    one-frame callers).  A ring that does not fit the status words is refused at its first frame: the kernels write the word unchecked."""
+    slot = 4 + per_frame * (k % ring) + r
+    if max(slot, 3 + per_frame * ring) >= STATUS_WORDS:
+        raise L.YondHipError(f"{ring} frames of {per_frame} range-guard words in flight need {4 + per_frame * ring} status words, a plan has "
+                             f"{STATUS_WORDS}: fewer STREAM_LANES")
+    return slot
+
+
+@contextlib.contextmanager
+def _lane_streams(plan, main, lanes):
+    """The stretch of a stream driver that queues on `lanes`: however it ends -- the consumer closing the generator, a hand-back raising --
+    the plan is back on lane 0 and the caller's stream continues behind everything queued on the other lanes."""
+    try:
+        yield
+    finally:
+        plan.lane = 0
+        for ln in lanes:
+            if ln is not main:
+                main.wait_stream(ln)
+
+
 def _iter_denoise_chain(lr, net, arch, pipe, p, log=None):
     """IterDenoise for a bare full frame on the device chain: both rounds are queued back to back (round 2 speculatively: its
     estimate needs round 1's output, not its numbers) and ONE synchronisation at the end delivers the parameter blocks.
@@ -1126,34 +1216,14 @@ def _iter_denoise_chain(lr, net, arch, pipe, p, log=None):
     two = pipe.get('iter', 'iter') == 'iter' and pipe.get('max_iter', 1) >= 1
     if two and pipe.get('max_iter', 1) > 1:
         return None
+    done = [(out1, b1, g1)]
     if two:
         mx = torch.empty(1, dtype=torch.float32, device=lr.device)
         mx.copy_(b1.prm[PRM['frame_max']:PRM['frame_max'] + 1])           # float64 holding the float32 maximum -> float32
-        out2, b2, g2 = _chain_round(lr, out1, 'collab', net, arch, pipe, p, slot=1, lr_max_dev=mx)
+        done.append(_chain_round(lr, out1, 'collab', net, arch, pipe, p, slot=1, lr_max_dev=mx))
     torch.cuda.current_stream().synchronize()
-    reg1, par1, fl1, info1 = _chain_result(b1)
-    if fl1 & (PRM_NO_FLAT_AREA | PRM_LUT_CAPACITY | PRM_BAD_ESTIMATE):
-        return None
-    if g1 is not None and g1.tripped():
-        return None                                      # an activation left fp16's range: the guarded host path recomputes
-    if log:
-        log(f"Self Est: K={par1[0]:.4f}, b={par1[1]:.4f} (beta1={reg1[0]:.3e}, beta2={reg1[1]:.3e})")
-    raw_dns, regs, params = [out1], [reg1], [par1]
-    if two:
-        reg2, par2, fl2, info2 = _chain_result(b2)
-        if fl2 & (PRM_NO_FLAT_AREA | PRM_LUT_CAPACITY):
-            return None
-        if log:
-            log(f"Iter 1 Est: K={par2[0]:.4f}, sigma={par2[1]:.4f} (beta1={reg2[0]:.3e}, beta2={reg2[1]:.3e})")
-        if not (fl2 & PRM_ROUND_ABORTED):                # :445-447: beta1 < 0 ends the image after round 1
-            if fl2 & PRM_BAD_ESTIMATE:
-                return None
-            if g2 is not None and g2.tripped():
-                return None
-            raw_dns.append(out2)
-            regs.append(reg2)
-            params.append(par2)
-    return dict(raw_dns=raw_dns, regs=regs, params=params, nle_info=info1)
+    outs, bufs, guards = zip(*done)
+    return _chain_settle(bufs, outs, guards, log)          # (a tripped guard: the guarded host path recomputes)
 
 
 def chain_applies_sidd(lr, lr_full, net, arch, pipe, p, biaslut=None):
@@ -1265,34 +1335,10 @@ def _iter_denoise_chain_sidd_group(items, net, arch, pipe, p, log=None):
         for q, o in zip(st, o2):
             q['out2'] = torch.cat(list(o), dim=-1).contiguous()
     torch.cuda.current_stream().synchronize()
-    trip1 = g1 is not None and g1.tripped()
-    trip2 = two and g2 is not None and g2.tripped()
-    results = []
-    for g, q in enumerate(st):
-        tag = f"[image {g} of the group] " if G > 1 else ""
-        reg1, par1, fl1, info1 = _chain_result(q['b1'])
-        if fl1 & (PRM_NO_FLAT_AREA | PRM_LUT_CAPACITY | PRM_BAD_ESTIMATE) or trip1:
-            results.append(None)
-            continue
-        if log:
-            log(f"{tag}Self Est: K={par1[0]:.4f}, b={par1[1]:.4f} (beta1={reg1[0]:.3e}, beta2={reg1[1]:.3e})")
-        raw_dns, regs, params = [q['out1']], [reg1], [par1]
-        if two:
-            reg2, par2, fl2, info2 = _chain_result(q['b2'])
-            if fl2 & (PRM_NO_FLAT_AREA | PRM_LUT_CAPACITY):
-                results.append(None)
-                continue
-            if log:
-                log(f"{tag}Iter 1 Est: K={par2[0]:.4f}, sigma={par2[1]:.4f} (beta1={reg2[0]:.3e}, beta2={reg2[1]:.3e})")
-            if not (fl2 & PRM_ROUND_ABORTED):                # :445-447: beta1 < 0 ends the image after round 1
-                if fl2 & PRM_BAD_ESTIMATE or trip2:
-                    results.append(None)
-                    continue
-                raw_dns.append(q['out2'])
-                regs.append(reg2)
-                params.append(par2)
-        results.append(dict(raw_dns=raw_dns, regs=regs, params=params, nle_info=info1))
-    return results
+    trips = [w is not None and w.tripped() for w in ((g1, g2) if two else (g1,))]         # (a round's guard watched the whole group: read once)
+    rs = ('1', '2')[:len(trips)]
+    return [_chain_settle([q['b' + r] for r in rs], [q['out' + r] for r in rs], trips, log, f"[image {g} of the group] " if G > 1 else "")
+            for g, q in enumerate(st)]
 
 
 def _frame_max(x):
@@ -1698,7 +1744,8 @@ def denoise_stream_groups(groups, net, arch, pipe, p=None, device=None, log=None
         plan.lane = 0 if lane is main else 1
         try:
             with torch.cuda.stream(lane):
-                outs, watch = _chain_denoise_blocks_group([it[0] for it in st['items']], net, arch, p0, [bufs(k, g, r) for g in range(G)], 4 + 2 * (k % RING) + r)
+                outs, watch = _chain_denoise_blocks_group([it[0] for it in st['items']], net, arch, p0, [bufs(k, g, r) for g in range(G)],
+                                                          _guard_slot(k, RING, r, 2))
                 cat = [torch.cat(list(o), dim=-1).contiguous() for o in outs]
                 fin = lane.record_event()
         finally:
@@ -1715,26 +1762,14 @@ def denoise_stream_groups(groups, net, arch, pipe, p=None, device=None, log=None
             res = IterDenoiseGroup(items, net, arch, pipe, ps=p0, log=log, biaslut=biaslut)
         else:
             st['fin2'].synchronize()
-            trip1 = st['g1'] is not None and st['g1'].tripped()
-            trip2 = st['g2'] is not None and st['g2'].tripped()
+            trips = [w is not None and w.tripped() for w in (st['g1'], st['g2'])]     # (a round's guard watched the whole group: read once)
             res = []
             for g in range(len(items)):
-                reg1, par1, fl1, info1 = _chain_result(bufs(k, g, 0))
-                reg2, par2, fl2, info2 = _chain_result(bufs(k, g, 1))
-                bad = bool(fl1 & (PRM_NO_FLAT_AREA | PRM_LUT_CAPACITY | PRM_BAD_ESTIMATE)) or trip1 or bool(fl2 & (PRM_NO_FLAT_AREA | PRM_LUT_CAPACITY))
-                aborted = bool(fl2 & PRM_ROUND_ABORTED)                       # :445-447
-                if not bad and not aborted:
-                    bad = bool(fl2 & PRM_BAD_ESTIMATE) or trip2
-                if bad:
-                    res.append(IterDenoise(items[g][0], net, arch, pipe, lr_full=items[g][1], p=p0, log=log, biaslut=biaslut))
+                one = _chain_settle([bufs(k, g, 0), bufs(k, g, 1)], [st['out1'][g], st['out2'][g]], trips)
+                if one is None:                        # (the chain stays on here: IterDenoise tries it once more, one image alone, and logs)
+                    one = IterDenoise(items[g][0], net, arch, pipe, lr_full=items[g][1], p=p0, log=log, biaslut=biaslut)
                     redone = True
-                    continue
-                raw_dns, regs, params = [st['out1'][g]], [reg1], [par1]
-                if not aborted:
-                    raw_dns.append(st['out2'][g])
-                    regs.append(reg2)
-                    params.append(par2)
-                res.append(dict(raw_dns=raw_dns, regs=regs, params=params, nle_info=info1))
+                res.append(one)
         if finish is not None:
             # on a stream of its own: the host has just waited for this group's last pass, and a host read inside `finish` must not wait for the estimates and
             # passes of the groups queued since
@@ -1759,37 +1794,36 @@ def denoise_stream_groups(groups, net, arch, pipe, p=None, device=None, log=None
         return dict(items=items, lr_cat=[], mx=[], chain=usable(items), g1=None, g2=None)
 
     live = {}
-    nxt = take()
-    k = 0
-    if nxt is not None:
-        live[0] = nxt
-        if nxt['chain']:
-            nxt['e1'] = est1(nxt, 0, main.record_event())
-    while k in live:
-        st = live[k]
-        nxt = take()                                  # (and mark the main stream) BEFORE queuing this group's network
-        ready = main.record_event()
-        if st['chain']:
-            st['out1'], st['g1'], st['fin1'] = round_(st, k, 0, st['e1'])      # D1(k)
+    with _lane_streams(plan, main, [lane2]):
+        nxt = take()
+        k = 0
         if nxt is not None:
-            live[k + 1] = nxt
+            live[0] = nxt
             if nxt['chain']:
-                nxt['e1'] = est1(nxt, k + 1, ready)                            # E1(k+1): under D1(k)
-        if st['chain']:
-            st['e2'] = est2(st, k)                                             # E2(k): behind D1(k), under D2(k-1)
+                nxt['e1'] = est1(nxt, 0, main.record_event())
+        while k in live:
+            st = live[k]
+            nxt = take()                                  # (and mark the main stream) BEFORE queuing this group's network
+            ready = main.record_event()
+            if st['chain']:
+                st['out1'], st['g1'], st['fin1'] = round_(st, k, 0, st['e1'])      # D1(k)
+            if nxt is not None:
+                live[k + 1] = nxt
+                if nxt['chain']:
+                    nxt['e1'] = est1(nxt, k + 1, ready)                            # E1(k+1): under D1(k)
+            if st['chain']:
+                st['e2'] = est2(st, k)                                             # E2(k): behind D1(k), under D2(k-1)
+            if k - 1 in live and live[k - 1]['chain']:
+                prev = live[k - 1]
+                prev['out2'], prev['g2'], prev['fin2'] = round_(prev, k - 1, 1, prev['e2'])    # D2(k-1)
+            if k - 2 in live:
+                yield release(live.pop(k - 2), k - 2)
+            k += 1
         if k - 1 in live and live[k - 1]['chain']:
             prev = live[k - 1]
-            prev['out2'], prev['g2'], prev['fin2'] = round_(prev, k - 1, 1, prev['e2'])    # D2(k-1)
-        if k - 2 in live:
-            yield release(live.pop(k - 2), k - 2)
-        k += 1
-    if k - 1 in live and live[k - 1]['chain']:
-        prev = live[k - 1]
-        prev['out2'], prev['g2'], prev['fin2'] = round_(prev, k - 1, 1, prev['e2'])
-    for j in sorted(live):
-        yield release(live.pop(j), j)
-    if lane2 is not main:
-        main.wait_stream(lane2)
+            prev['out2'], prev['g2'], prev['fin2'] = round_(prev, k - 1, 1, prev['e2'])
+        for j in sorted(live):
+            yield release(live.pop(j), j)
 
 
 STREAM_GROUPS = True                # (module attribute: False = the evaluation drivers take one group at a time, for A/B)
@@ -1847,53 +1881,40 @@ def denoise_stream_batches(frames, B, net, arch, pipe, p=None, device=None):
         batch, outs, watch, fin = item
         fin.synchronize()
         trip = watch is not None and watch.tripped()
-        res = []
-        for b, lr in enumerate(batch):
-            reg, par, flags, info = _chain_result(bufs(k, b))
-            if flags & (PRM_NO_FLAT_AREA | PRM_LUT_CAPACITY | PRM_BAD_ESTIMATE) or trip:
-                global DEVICE_CHAIN
-                DEVICE_CHAIN = False
-                try:
-                    res.append(IterDenoise(lr, net, arch, pipe, p=p0))
-                finally:
-                    DEVICE_CHAIN = True
-            else:
-                res.append(dict(raw_dns=[outs[b]], regs=[reg], params=[par], nle_info=info))
-        return res
+        return [_chain_settle([bufs(k, b)], [outs[b]], [trip]) or _host_chain_redo(lr, net, arch, pipe, p0) for b, lr in enumerate(batch)]
 
     batch = take()
     if not batch:
         return
     k = 0
-    est = estimate(batch, 0, main.record_event())
     pending = []
-    while batch:
-        nxt = take()                                   # (and mark the main stream) BEFORE queuing this batch's network
-        ready = main.record_event()
-        lane = lanes[k % NL]
-        lane.wait_event(est)
-        plan.lane = k % NL
-        try:
-            with torch.cuda.stream(lane):
-                outs, watch = _chain_denoise_frames(batch, net, arch, p0, [bufs(k, b) for b in range(len(batch))], 4 + (k % RING))
-                fin = lane.record_event()
-        finally:
-            plan.lane = 0
-        if lane is not main:
-            for o in outs:
-                o.record_stream(main)
-        cur = (batch, outs, watch, fin)
-        if nxt:
-            est = estimate(nxt, k + 1, ready)
-        pending.append((cur, k))
-        if len(pending) > NL:
+    with _lane_streams(plan, main, lanes):
+        est = estimate(batch, 0, main.record_event())
+        while batch:
+            nxt = take()                                   # (and mark the main stream) BEFORE queuing this batch's network
+            ready = main.record_event()
+            lane = lanes[k % NL]
+            lane.wait_event(est)
+            plan.lane = k % NL
+            try:
+                with torch.cuda.stream(lane):
+                    outs, watch = _chain_denoise_frames(batch, net, arch, p0, [bufs(k, b) for b in range(len(batch))], _guard_slot(k, RING))
+                    fin = lane.record_event()
+            finally:
+                plan.lane = 0
+            if lane is not main:
+                for o in outs:
+                    o.record_stream(main)
+            cur = (batch, outs, watch, fin)
+            if nxt:
+                est = estimate(nxt, k + 1, ready)
+            pending.append((cur, k))
+            if len(pending) > NL:
+                yield from release(*pending.pop(0))
+            batch = nxt
+            k += 1
+        while pending:
             yield from release(*pending.pop(0))
-        batch = nxt
-        k += 1
-    while pending:
-        yield from release(*pending.pop(0))
-    for ln in lanes[1:]:
-        main.wait_stream(ln)
 
 
 def IterDenoiseBatch(frames, net, arch, pipe, p=None, device=None):
@@ -2107,17 +2128,12 @@ def _denoise_stream_chain(frames, net, arch, pipe, p0, device):
     def release(item):
         lr, pk, out, buf, watch, fin = item
         fin.synchronize()
-        reg, par, flags, info = _chain_result(buf)
-        if flags & (PRM_NO_FLAT_AREA | PRM_LUT_CAPACITY | PRM_BAD_ESTIMATE) or (watch is not None and watch.tripped()):
-            global DEVICE_CHAIN
-            DEVICE_CHAIN = False
-            try:
-                return IterDenoise(lr, net, arch, pipe, p=pk)
-            finally:
-                DEVICE_CHAIN = True
+        res = _chain_settle([buf], [out], [watch])
+        if res is None:
+            return _host_chain_redo(lr, net, arch, pipe, pk)
         if out.device.type == 'cuda':
             out.record_stream(main)                              # (allocated on its lane's stream, handed to the caller's)
-        return dict(raw_dns=[out], regs=[reg], params=[par], nle_info=info)
+        return res
 
     it = iter(frames)
     try:
@@ -2127,7 +2143,7 @@ def _denoise_stream_chain(frames, net, arch, pipe, p0, device):
     k_frame = 0
     nxt = estimate(f, main.record_event(), k_frame)
     pending = []
-    try:
+    with _lane_streams(plan, main, lanes):
         while nxt is not None:
             lr, pk, buf, est_done = nxt
             try:                               # take the next frame (and mark the main stream) BEFORE queuing this one's network
@@ -2139,7 +2155,7 @@ def _denoise_stream_chain(frames, net, arch, pipe, p0, device):
             lane.wait_event(est_done)          # (and, through the estimate's own wait, the frame as the main stream uploaded it)
             plan.lane = k_frame % NL
             with torch.cuda.stream(lane):
-                out, watch = _chain_denoise(lr, net, arch, pk, buf, 4 + k_frame % RING)
+                out, watch = _chain_denoise(lr, net, arch, pk, buf, _guard_slot(k_frame, RING))
                 fin = lane.record_event()
             plan.lane = 0
             k_frame += 1
@@ -2149,10 +2165,6 @@ def _denoise_stream_chain(frames, net, arch, pipe, p0, device):
                 yield release(pending.pop(0))
         while pending:
             yield release(pending.pop(0))
-    finally:
-        plan.lane = 0
-        for ln in lanes[1:]:
-            main.wait_stream(ln)               # (the caller's stream continues behind everything queued here)
 
 
 LANE_PIPELINES_ONCE = False         # A/B: 'once' as independent lane pipelines too (no side stream)
@@ -2177,50 +2189,32 @@ def _denoise_lanes(frames, net, arch, pipe, p0, device, rounds):
 
     def release(st, k):
         st['fin'].synchronize()
-        reg1, par1, fl1, info1 = _chain_result(bufs(k, 0))
-        bad = bool(fl1 & (PRM_NO_FLAT_AREA | PRM_LUT_CAPACITY | PRM_BAD_ESTIMATE)) or (st['g1'] is not None and st['g1'].tripped())
-        aborted = False
-        if rounds == 2:
-            reg2, par2, fl2, info2 = _chain_result(bufs(k, 1))
-            bad = bad or bool(fl2 & (PRM_NO_FLAT_AREA | PRM_LUT_CAPACITY))
-            aborted = bool(fl2 & PRM_ROUND_ABORTED)                           # :445-447: beta1 < 0 ends the image after round 1
-            if not bad and not aborted:
-                bad = bool(fl2 & PRM_BAD_ESTIMATE) or (st['g2'] is not None and st['g2'].tripped())
-        if bad:                                                               # a branch the chain leaves to the host-side path
-            global DEVICE_CHAIN
-            DEVICE_CHAIN = False
-            try:
-                return IterDenoise(st['lr'], net, arch, pipe, p=st['p'])
-            finally:
-                DEVICE_CHAIN = True
-        raw_dns, regs, params = [st['out1']], [reg1], [par1]
-        if rounds == 2 and not aborted:
-            raw_dns.append(st['out2'])
-            regs.append(reg2)
-            params.append(par2)
-        return dict(raw_dns=raw_dns, regs=regs, params=params, nle_info=info1)
+        rs = range(rounds)
+        return (_chain_settle([bufs(k, r) for r in rs], [st[f'out{r + 1}'] for r in rs], [st[f'g{r + 1}'] for r in rs])
+                or _host_chain_redo(st['lr'], net, arch, pipe, st['p']))
 
     pending = []
     k = 0
-    try:
+    with _lane_streams(plan, main, lanes):
         for f in frames:
+            slots = [_guard_slot(k, RING, r, 2) for r in range(rounds)]       # (a ring that does not fit is refused before anything is queued)
             lr, pk = _frame_item(f, p0, device)                               # (a host array is uploaded on the main stream)
             lane = lanes[k % NL]
             if lane is not main:
                 lane.wait_event(main.record_event())                          # the frame as it stood when it was handed in
-            st = dict(lr=lr, p=pk, g2=None)
+            st = dict(lr=lr, p=pk)
             plan.lane = k % NL
             try:
                 with torch.cuda.stream(lane):
                     b1 = bufs(k, 0)
                     _chain_estimate(lr, None, 'self', pipe, pk, b1)                                              # E1
-                    st['out1'], st['g1'] = _chain_denoise(lr, net, arch, pk, b1, 4 + 2 * (k % RING))           # D1
+                    st['out1'], st['g1'] = _chain_denoise(lr, net, arch, pk, b1, slots[0])                       # D1
                     if rounds == 2:
                         mx = torch.empty(1, dtype=torch.float32, device=main.device)
                         mx.copy_(b1.prm[PRM['frame_max']:PRM['frame_max'] + 1])                                  # float64 holding the float32 maximum -> float32
                         _chain_estimate(lr, st['out1'], 'collab', pipe, pk, bufs(k, 1), lr_max_dev=mx)           # E2
                         st['mx'] = mx
-                        st['out2'], st['g2'] = _chain_denoise(lr, net, arch, pk, bufs(k, 1), 4 + 2 * (k % RING) + 1)    # D2
+                        st['out2'], st['g2'] = _chain_denoise(lr, net, arch, pk, bufs(k, 1), slots[1])           # D2
                     st['fin'] = lane.record_event()
             finally:
                 plan.lane = 0
@@ -2234,10 +2228,6 @@ def _denoise_lanes(frames, net, arch, pipe, p0, device, rounds):
                 yield release(*pending.pop(0))
         while pending:
             yield release(*pending.pop(0))
-    finally:
-        plan.lane = 0
-        for ln in lanes[1:]:
-            main.wait_stream(ln)
 
 
 STREAM_ITER = True                  # (module attribute: False = 'iter' frames one at a time, for A/B)
@@ -2281,27 +2271,8 @@ def _denoise_stream_chain_iter(frames, net, arch, pipe, p0, device):
 
     def release(st, k):
         st['fin2'].synchronize()
-        b1, b2 = bufs(k, 0), bufs(k, 1)
-        reg1, par1, fl1, info1 = _chain_result(b1)
-        reg2, par2, fl2, info2 = _chain_result(b2)
-        bad = bool(fl1 & (PRM_NO_FLAT_AREA | PRM_LUT_CAPACITY | PRM_BAD_ESTIMATE)) or (st['g1'] is not None and st['g1'].tripped())
-        bad = bad or bool(fl2 & (PRM_NO_FLAT_AREA | PRM_LUT_CAPACITY))
-        aborted = bool(fl2 & PRM_ROUND_ABORTED)                               # :445-447: beta1 < 0 ends the image after round 1
-        if not bad and not aborted:
-            bad = bool(fl2 & PRM_BAD_ESTIMATE) or (st['g2'] is not None and st['g2'].tripped())
-        if bad:                                                               # a branch the chain leaves to the host-side path
-            global DEVICE_CHAIN
-            DEVICE_CHAIN = False
-            try:
-                return IterDenoise(st['lr'], net, arch, pipe, p=st['p'])
-            finally:
-                DEVICE_CHAIN = True
-        raw_dns, regs, params = [st['out1']], [reg1], [par1]
-        if not aborted:
-            raw_dns.append(st['out2'])
-            regs.append(reg2)
-            params.append(par2)
-        return dict(raw_dns=raw_dns, regs=regs, params=params, nle_info=info1)
+        return (_chain_settle([bufs(k, 0), bufs(k, 1)], [st['out1'], st['out2']], [st['g1'], st['g2']])
+                or _host_chain_redo(st['lr'], net, arch, pipe, st['p']))
 
     lane2 = _side_stream(main.device, 'net1') if STREAM_LANES > 1 else main     # second passes on a stream of their own: D2(k-1) beside D1(k)
     plan = _plan_of(net, main.device)
@@ -2311,7 +2282,7 @@ def _denoise_stream_chain_iter(frames, net, arch, pipe, p0, device):
         plan.lane = 0 if lane2 is main else 1
         try:
             with torch.cuda.stream(lane2):
-                st['out2'], st['g2'] = _chain_denoise(st['lr'], net, arch, st['p'], bufs(k, 1), 4 + 2 * (k % RING) + 1)
+                st['out2'], st['g2'] = _chain_denoise(st['lr'], net, arch, st['p'], bufs(k, 1), _guard_slot(k, RING, 1, 2))
                 st['fin2'] = lane2.record_event()
         finally:
             plan.lane = 0
@@ -2325,33 +2296,32 @@ def _denoise_stream_chain_iter(frames, net, arch, pipe, p0, device):
         return
     live = {}                                                                 # frame index -> its state
     k = 0
-    live[0] = dict(lr=f, p=fp)
-    live[0]['e1'] = est1(f, fp, main.record_event(), 0)
-    while k in live:
-        st = live[k]
-        try:                               # take the next frame (and mark the main stream) BEFORE queuing this one's network
-            f_next, p_next = _frame_item(next(it), p0, device)
-            ready = main.record_event()
-        except StopIteration:
-            f_next = None
-        main.wait_event(st['e1'])
-        st['out1'], st['g1'] = _chain_denoise(st['lr'], net, arch, st['p'], bufs(k, 0), 4 + 2 * (k % RING))       # D1(k)
-        st['fin1'] = main.record_event()
-        if f_next is not None:
-            live[k + 1] = dict(lr=f_next, p=p_next)
-            live[k + 1]['e1'] = est1(f_next, p_next, ready, k + 1)                     # E1(k+1): under D1(k)
-        st['e2'] = est2(st, k)                                                # E2(k): behind D1(k), under D2(k-1)
+    with _lane_streams(plan, main, [lane2]):
+        live[0] = dict(lr=f, p=fp)
+        live[0]['e1'] = est1(f, fp, main.record_event(), 0)
+        while k in live:
+            st = live[k]
+            try:                               # take the next frame (and mark the main stream) BEFORE queuing this one's network
+                f_next, p_next = _frame_item(next(it), p0, device)
+                ready = main.record_event()
+            except StopIteration:
+                f_next = None
+            main.wait_event(st['e1'])
+            st['out1'], st['g1'] = _chain_denoise(st['lr'], net, arch, st['p'], bufs(k, 0), _guard_slot(k, RING, 0, 2))       # D1(k)
+            st['fin1'] = main.record_event()
+            if f_next is not None:
+                live[k + 1] = dict(lr=f_next, p=p_next)
+                live[k + 1]['e1'] = est1(f_next, p_next, ready, k + 1)                     # E1(k+1): under D1(k)
+            st['e2'] = est2(st, k)                                                # E2(k): behind D1(k), under D2(k-1)
+            if k - 1 in live:
+                round2(live[k - 1], k - 1)                                        # D2(k-1)
+            if k - 2 in live:
+                yield release(live.pop(k - 2), k - 2)
+            k += 1
         if k - 1 in live:
-            round2(live[k - 1], k - 1)                                        # D2(k-1)
-        if k - 2 in live:
-            yield release(live.pop(k - 2), k - 2)
-        k += 1
-    if k - 1 in live:
-        round2(live[k - 1], k - 1)
-    for j in sorted(live):
-        yield release(live.pop(j), j)
-    if lane2 is not main:
-        main.wait_stream(lane2)
+            round2(live[k - 1], k - 1)
+        for j in sorted(live):
+            yield release(live.pop(j), j)
 
 
 _SIDE_STREAMS = {}
