@@ -704,6 +704,35 @@ int yond_adam_step_f32(float* p, const float* g, float* m, float* v, size_t n, d
  * of the caller's, e.g. a non-finite loss). */
 int yond_adam_step_dev_f32(float* p, const float* g, float* m, float* v, size_t n, double beta1, double beta2, double eps,
                            const float* hyp, const int* status, void* stream);
+/* Training-mode BatchNorm2d + ReLU and its backward (csrc/bn_train.hip; DnCNN's middle layers, archs/comp.py:18-26) on y [M][C] float32 --
+ * an [N][H][W][C] tensor with M = N H W values per channel.  Four entries, six launches, no allocation, no float atomics: every result is
+ * bitwise reproducible from run to run.
+ *   yond_bn_stats_f32       Sy = sum y, Syy = sum y y per channel in float64 (workgroup partials in ws, added in a fixed order by a finish
+ *                           launch), then  mean = Sy / M,  var = max(Syy / M - mean^2, 0) (biased),  rstd = 1 / sqrt(var + eps),
+ *                           scale = gamma rstd,  shift = beta - mean scale -- all in float64, each rounded to float32 once.
+ *                           stat [4][C]: mean, rstd, scale, shift.   pending [2][C]: the running statistics this batch WOULD leave,
+ *                           (1 - momentum) running_mean + momentum mean  and  (1 - momentum) running_var + momentum var M / (M - 1)
+ *                           (momentum: torch's, the weight of the new value; formed in float64, rounded once).  running_mean / running_var
+ *                           are only read: the caller commits `pending` once the step's verdict is in.
+ *   yond_bn_apply_relu_f32  out = max(fmaf(y, scale, shift), 0); a NaN stays a NaN (torch's ReLU).
+ *   yond_bn_bwd_reduce_f32  with g = dout [fmaf(y, scale, shift) > 0] and yh = (y - mean) rstd (two float32 roundings):
+ *                           dbeta = sum g, dgamma = sum g yh, float64 partials (g yh is exact there), fixed order, rounded to float32 once.
+ *   yond_bn_bwd_apply_f32   dy = scale * fmaf(-yh, float32(dgamma / M), g - float32(dbeta / M))   (the divisions in float64).
+ * The ReLU mask of the two backward entries is RECOMPUTED from (y, scale, shift) with the forward's own fmaf -- the same instruction on the
+ * same three float32 values, so it is the forward's mask element for element -- not stored.
+ * ws: yond_bn_train_ws_bytes(M, C) bytes, 8-byte aligned, fully overwritten by each reducing entry (stats and bwd_reduce may share it in
+ * stream order).  The query is host only and returns 0 for a shape the entries refuse.
+ * Refused (YOND_EINVAL, nothing launched): a null pointer, C % 32 != 0, C outside 32..128, M < 2, a tensor / stat pointer (and, for
+ * bwd_apply, dgamma / dbeta) not 16-byte aligned, ws misaligned or smaller than the query's answer, eps < 0 or momentum outside [0, 1]. */
+size_t yond_bn_train_ws_bytes(size_t M, int C);
+int yond_bn_stats_f32(const float* y, size_t M, int C, const float* gamma, const float* beta, const float* running_mean,
+                      const float* running_var, double eps, double momentum, float* stat, float* pending, void* ws, size_t ws_bytes,
+                      void* stream);
+int yond_bn_apply_relu_f32(const float* y, const float* stat, size_t M, int C, float* out, void* stream);
+int yond_bn_bwd_reduce_f32(const float* y, const float* dout, const float* stat, size_t M, int C, float* dgamma, float* dbeta, void* ws,
+                           size_t ws_bytes, void* stream);
+int yond_bn_bwd_apply_f32(const float* y, const float* dout, const float* stat, const float* dgamma, const float* dbeta, size_t M, int C,
+                          float* dy, void* stream);
 
 /* Measurement aid (bench.py; not on the reference's path): one wave sleeps for `us` microseconds (<= 5 s) of wall time and
  * writes out[0] = elapsed shader cycles (s_memtime), out[1] = elapsed 100 MHz reference ticks (s_memrealtime): the clock

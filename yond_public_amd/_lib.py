@@ -131,6 +131,11 @@ PROTOTYPES = {
     "yond_charbonnier_loss_f32": [vp, vp, sz, f64, vp, vp, vp],
     "yond_adam_step_f32": [vp, vp, vp, vp, sz, f64, f64, f64, f64, i32, vp],
     "yond_adam_step_dev_f32": [vp, vp, vp, vp, sz, f64, f64, f64, vp, vp, vp],
+    "yond_bn_train_ws_bytes": [sz, i32],
+    "yond_bn_stats_f32": [vp, sz, i32, vp, vp, vp, vp, f64, f64, vp, vp, vp, sz, vp],
+    "yond_bn_apply_relu_f32": [vp, vp, sz, i32, vp, vp],
+    "yond_bn_bwd_reduce_f32": [vp, vp, vp, sz, i32, vp, vp, vp, sz, vp],
+    "yond_bn_bwd_apply_f32": [vp, vp, vp, vp, vp, sz, i32, vp, vp],
     "yond_frame_params_f64": [vp, vp, i32, f64, f64, f64, i32, vp, vp, vp, vp],
     "yond_frame_chain_f64": [vp, vp, i32, f64, f64, f64, i32, vp, vp, vp, vp, vp, vp],
     "yond_bias_lut_dev_f64": [vp, i32, vp, vp, vp],
@@ -167,7 +172,7 @@ PROTOTYPES = {
 _SIZE_T_RET = {"yond_select_ws_bytes", "yond_nle_ws_bytes", "yond_lut_ws_bytes", "yond_bias_lut_big_scratch", "yond_bias_points_scratch",
                "yond_conv_wgrad_ws_bytes", "yond_conv_wgrad_split_ws_bytes",
                "yond_est_head_ws_bytes", "yond_ransac_compact_ws_bytes", "yond_ransac_ws_bytes",
-               "yond_illum_ws_bytes"}
+               "yond_illum_ws_bytes", "yond_bn_train_ws_bytes"}
 
 
 class YondHipError(RuntimeError):

@@ -46,8 +46,8 @@ class DnCNN(_HipDenoiser):
         """As _HipDenoiser._get_plan, with the BatchNorm buffers in the key (load_state_dict writes them in place) and the refusal of
         batch statistics at every call (.train() does not touch a parameter)."""
         if self.training and self.args['use_bn']:
-            raise L.YondHipError("DnCNN: the module is in .train() mode and has BatchNorm layers: batch statistics are not built on the HIP "
-                                 "path (call .eval(): the running statistics are folded into the convolutions' epilogues)")
+            raise L.YondHipError("DnCNN: the module is in .train() mode and has BatchNorm layers: this forward is inference (call .eval(): the "
+                                 "running statistics are folded into the convolutions' epilogues); batch statistics run in train.TrainStep")
         plist = getattr(self, '_plist', None)
         if plist is None:
             plist = self._plist = list(self.parameters()) + list(self.buffers())

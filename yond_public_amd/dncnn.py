@@ -7,8 +7,9 @@ libyond_hip.so: a straight stack of full-resolution 3x3 convolutions, blind (no 
 Every middle layer is the denoisers' convolution (`DenoiserPlan._conv`: split-operand fp16-MFMA products at fp32 accuracy by default,
 the fp32-input MFMA kernels for 'fp32-mfma' and for the range guard's re-run; 'fp16' rounds the operands to half, algo 4).  ReLU is
 LeakyReLU with slope 0 in the epilogue, BatchNorm (running statistics) is folded on the host, in float64, into the epilogue's
-(escale, eshift):  escale = gamma / sqrt(running_var + eps),  eshift = beta - running_mean * escale.  Batch statistics are not
-built: a module in .train() mode with BatchNorm layers is refused.
+(escale, eshift):  escale = gamma / sqrt(running_var + eps),  eshift = beta - running_mean * escale.  This plan is inference:
+a module in .train() mode with BatchNorm layers is refused here (batch statistics and their backward run in train.TrainStep only,
+csrc/bn_train.hip).
 
 The tensors between the layers are plain [N][H][W][nf] float32 (every kernel form of the 3x3 layers takes and stores them, on all
 three precisions and on the guard's re-run); the split-plane producer / consumer forms exist for PAIRS of layers (one producer,
@@ -68,8 +69,8 @@ class DnCNNPlan(DenoiserPlan):
         self.depth = int(args['depth'])
         layers = list(module.dncnn)
         if module.training and any(isinstance(m, torch.nn.BatchNorm2d) for m in layers):
-            raise L.YondHipError("DnCNN: the module is in .train() mode and has BatchNorm layers: batch statistics are not built on the HIP "
-                                 "path (call .eval(): the running statistics are folded into the convolutions' epilogues)")
+            raise L.YondHipError("DnCNN: the module is in .train() mode and has BatchNorm layers: this forward is inference (call .eval(): the "
+                                 "running statistics are folded into the convolutions' epilogues); batch statistics run in train.TrainStep")
         dev = self.dev
         first, last = layers[0], layers[-1]
         self.conv_in_w, self.conv_in_b = self._pack_conv_in(first.weight, first.bias)

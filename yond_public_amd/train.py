@@ -16,7 +16,8 @@ to multiples of 32, with every convolution -- forward, data gradient and weight 
   * loss and optimiser: yond_l1_loss_f32, yond_adam_step_f32.
 torch.autograd only strings the layers together (custom Functions) and differentiates the elementwise glue (SiLU, LeakyReLU,
 FiLM scale / shift and its three tiny sigma-MLPs, residual adds), which is <0.1 % of the step's arithmetic.
-Scope: GuidedResUnet and UNetSeeInDark (the two nets the reference's runfiles/Gaussian/*.yml train) / fp32; weights are re-packed on the host every step (fine at nf = 8 ... 32; a production loop would keep
+Scope: GuidedResUnet, SNRnet and UNetSeeInDark (the nets the reference's runfiles/Gaussian/*.yml train) and the comparison denoiser DnCNN
+(archs/comp.py:3-33, runfiles/Gaussian/DnCNN_5to50_norm.yml: BatchNorm on the batch statistics with its backward, csrc/bn_train.hip, single process) / fp32; weights are re-packed on the host every step (fine at nf = 8 ... 32; a production loop would keep
 packed weights resident).  Data-parallel: one process per GPU, every rank steps on its own batches, `GradReducer` averages the
 gradients in two 25 MB buckets launched from backward's hooks (the only collective of training: 44.7 MB per step).
 Pinned by tests/golden/train.npz (loss, gradients and updated weights of the reference's own step on the same inputs) and
@@ -246,7 +247,7 @@ class _Conv3x3(torch.autograd.Function):
         x = x.contiguous()
         y = _conv_fwd(plan, w, b, 3, stride, [cin], [x], N, H, W, res=None if res is None else res.contiguous())
         ctx.save_for_backward(x, w)
-        ctx.plan, ctx.stride, ctx.need_dx, ctx.has_res = plan, stride, need_dx, res is not None
+        ctx.plan, ctx.stride, ctx.need_dx, ctx.has_res, ctx.has_bias = plan, stride, need_dx, res is not None, b is not None
         return y
 
     @staticmethod
@@ -275,7 +276,8 @@ class _Conv3x3(torch.autograd.Function):
                            xf=lambda t: t.flip(2, 3).transpose(0, 1).contiguous())          # [cin][cout][2-ky][2-kx]
             dx = _pad_c(dx[..., :cin], cin_p) if dx.shape[-1] != cin_p else dx
         _join(plan)
-        return dx, dw, db, None, None, None, (dy if ctx.has_res else None)
+        # (a layer without bias -- DnCNN's middle and last convolutions -- was called with b = None: autograd refuses a gradient for it)
+        return dx, dw, (db if ctx.has_bias else None), None, None, None, (dy if ctx.has_res else None)
 
 
 class _Conv3x3Cat(torch.autograd.Function):
@@ -437,6 +439,57 @@ class _FilmSilu(torch.autograd.Function):
         L.check(ctx.plan.lib.yond_film_silu_bwd_f32(L.ptr(z), L.ptr(tk), L.ptr(tb), L.ptr(dout), L.ptr(dz), L.ptr(dtk), L.ptr(dtb), N, H * W, C,
                                                     L.stream()), "yond_film_silu_bwd_f32")
         return dz, dtk, dtb, None
+
+
+class _BatchNormRelu(torch.autograd.Function):
+    """ReLU(BatchNorm2d(y)) on the BATCH statistics (archs/comp.py:20-23 in .train() mode) over y [N][H][W][C], forward and backward as
+    two entries each of csrc/bn_train.hip (statistics + apply; reduction + apply).  `bn`: the layer's device state (TrainStep._bn_state):
+    the running statistics it reads, `stat` (mean, rstd, scale, shift) and `pending` (the running statistics this batch would leave --
+    TrainStep commits them once the step's verdict is in).  Nothing is read back to the host; beside the output and gradient tensors
+    (torch's allocator, as every Function here) every buffer exists before the step.  The backward is linear in dout: at loss scale S,
+    dgamma and dbeta come out at scale S and are unscaled with the flat gradient.  The ReLU mask is recomputed from (y, scale, shift)."""
+
+    @staticmethod
+    def forward(ctx, y, gamma, beta, bn, plan):
+        y = y.contiguous()
+        N, H, W, C = y.shape
+        M = N * H * W
+        ws = _bn_ws(plan, M, C)
+        out = torch.empty_like(y)
+        L.check(plan.lib.yond_bn_stats_f32(L.ptr(y), M, C, L.ptr(gamma), L.ptr(beta), L.ptr(bn.rm), L.ptr(bn.rv), bn.eps, bn.momentum, L.ptr(bn.stat),
+                                           L.ptr(bn.pending), L.ptr(ws), ws.numel() * 8, L.stream()), "yond_bn_stats_f32")
+        L.check(plan.lib.yond_bn_apply_relu_f32(L.ptr(y), L.ptr(bn.stat), M, C, L.ptr(out), L.stream()), "yond_bn_apply_relu_f32")
+        ctx.save_for_backward(y)
+        ctx.bn, ctx.plan = bn, plan
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        y, = ctx.saved_tensors
+        bn, plan = ctx.bn, ctx.plan
+        dout = dout.contiguous()
+        N, H, W, C = y.shape
+        M = N * H * W
+        ws = _bn_ws(plan, M, C)
+        dgb = torch.empty((2, C), dtype=torch.float32, device=y.device)
+        dy = torch.empty_like(y)
+        L.check(plan.lib.yond_bn_bwd_reduce_f32(L.ptr(y), L.ptr(dout), L.ptr(bn.stat), M, C, L.ptr(dgb[0]), L.ptr(dgb[1]), L.ptr(ws), ws.numel() * 8,
+                                                L.stream()), "yond_bn_bwd_reduce_f32")
+        L.check(plan.lib.yond_bn_bwd_apply_f32(L.ptr(y), L.ptr(dout), L.ptr(bn.stat), L.ptr(dgb[0]), L.ptr(dgb[1]), M, C, L.ptr(dy), L.stream()),
+                "yond_bn_bwd_apply_f32")
+        return dy, dgb[0], dgb[1], None, None
+
+
+def _bn_ws(plan, M, C):
+    """The BatchNorm reductions' partial sums: one float64 workspace per plan, grown to the largest layer's need (every launch that uses
+    it is on the step's main stream, in order)."""
+    need = int(plan.lib.yond_bn_train_ws_bytes(M, C))
+    if not need:
+        raise L.YondHipError(f"BatchNorm on the HIP path takes 32, 64, 96 or 128 channels and at least two values per channel, got C = {C}, M = {M}")
+    ws = getattr(plan, 'bn_ws', None)
+    if ws is None or ws.numel() * 8 < need:
+        ws = plan.bn_ws = torch.empty(need // 8, dtype=torch.float64, device=plan.dev); plan.gen += 1     # (captured steps hold the old one)
+    return ws
 
 
 class _FilmMLP(torch.autograd.Function):
@@ -629,7 +682,11 @@ class _ConvT2x2(torch.autograd.Function):
 
 
 class TrainStep:
-    """One optimisation step of a yond_public_amd.archs.GuidedResUnet or UNetSeeInDark (parameter names / shapes of the reference)."""
+    """One optimisation step of a yond_public_amd.archs.GuidedResUnet, SNRnet, UNetSeeInDark or DnCNN (parameter names / shapes of the
+    reference).  A step always trains: DnCNN's BatchNorm layers normalise with the batch statistics whatever module.training says
+    (`net(x)` itself keeps refusing .train() mode: inference folds the running statistics).  BatchNorm and the loss scale: the backward is
+    linear in dout, so dgamma / dbeta come out at scale S and are unscaled with the flat gradient -- nothing special; the forward does not
+    depend on S, so the attempts of a redone step leave the same pending running statistics, committed once (_bn_commit)."""
 
     def __init__(self, module, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, charbonnier=False, ddp=None, conv='split', loss_scale=None, graph=True):
         """conv: 'split' -- forward and data-gradient 3x3 convolutions as fp32-accurate split-operand products on the fp16 matrix
@@ -654,6 +711,11 @@ class TrainStep:
         self._graphs, self._seen = {}, {}
         self.m = module
         self.dev = next(module.parameters()).device
+        bns = [(i, l) for i, l in enumerate(module.dncnn) if isinstance(l, torch.nn.BatchNorm2d)] if type(module).__name__ == 'DnCNN' else []
+        if bns and ddp is not False and D._active():
+            raise L.YondHipError("TrainStep: DnCNN with BatchNorm layers under a process group is not built: the reference's DDP normalises every "
+                                 "rank's batch with its own statistics and broadcasts rank 0's buffers, and neither that exchange nor SyncBatchNorm "
+                                 "exists on the HIP path (train it in one process, or with use_bn: False)")
         self.plan = _plan(self.dev)
         if conv not in ('split', 'fp32'):
             raise ValueError(f"conv must be 'split' or 'fp32', got {conv!r}")
@@ -680,6 +742,7 @@ class TrainStep:
         self.state = {k: (self.adam_m[o:o + c].view(self.params[k].shape), self.adam_v[o:o + c].view(self.params[k].shape))
                       for k, (o, c) in self.slots.items()}
         self.t = 0
+        self._bn = self._bn_state(bns)
         self.reducer = None
         if ddp is not False and D._active():
             D.broadcast_params(self.params.values(), src=0)         # DDP's constructor: every rank starts from rank 0's weights
@@ -763,13 +826,83 @@ class TrainStep:
             out = out * ub[:, None, None, None]
         return out.permute(0, 3, 1, 2)
 
+    # -- DnCNN: batch statistics ------------------------------------------------------------------------------------------------
+    def _bn_state(self, bns):
+        """The device state of the module's BatchNorm layers ({index in module.dncnn: namespace}; empty without any).  gamma and beta are
+        parameters: they live in the arena and the one Adam launch steps them.  The buffers stay outside it: running_mean / running_var of
+        ALL layers become views of one flat tensor (`bn_running`, per layer [2][C]), num_batches_tracked of one int64 tensor, so that a step
+        commits them with two launches; `bn_pending` (same layout) takes what the forward kernels would leave, `bn_stat` (per layer [4][C])
+        the batch's mean, rstd, scale, shift for the backward.  As for the parameters: .to() / .float() on the module afterwards detaches them."""
+        if not bns:
+            return {}
+        for _, l in bns:
+            if l.momentum is None or not l.affine or not l.track_running_stats:
+                raise L.YondHipError("TrainStep: BatchNorm2d needs a momentum, affine=True and track_running_stats=True (archs/comp.py:22)")
+            if l.running_mean.dtype != torch.float32 or l.running_mean.device != self.arena.device:
+                raise L.YondHipError(f"TrainStep: the BatchNorm buffers must be float32 tensors on {self.dev}")
+        tot = sum(l.num_features for _, l in bns)
+        self.bn_running = torch.empty(2 * tot, dtype=torch.float32, device=self.dev)
+        self.bn_pending = torch.zeros(2 * tot, dtype=torch.float32, device=self.dev)
+        self.bn_stat = torch.zeros(4 * tot, dtype=torch.float32, device=self.dev)
+        self.bn_nbt = torch.stack([l.num_batches_tracked.detach().to(self.dev, torch.int64) for _, l in bns])
+        state, off = {}, 0
+        for j, (i, l) in enumerate(bns):
+            c = l.num_features
+            rm, rv = self.bn_running[2 * off:2 * off + c], self.bn_running[2 * off + c:2 * off + 2 * c]
+            rm.copy_(l.running_mean.data)
+            rv.copy_(l.running_var.data)
+            l.running_mean.data, l.running_var.data, l.num_batches_tracked.data = rm, rv, self.bn_nbt[j]
+            state[i] = types.SimpleNamespace(rm=rm, rv=rv, eps=float(l.eps), momentum=float(l.momentum), stat=self.bn_stat[4 * off:4 * off + 4 * c],
+                                             pending=self.bn_pending[2 * off:2 * off + 2 * c])
+            off += c
+        return state
+
+    def _bn_commit(self):
+        """The step is through (no range trip, a finite loss): the running statistics its forward left in `bn_pending` become the module's,
+        num_batches_tracked advances -- once per completed step, however many attempts the loss scale took (every attempt's forward
+        reads the same committed statistics and the same batch, and does not depend on S: it writes the same pending values).  Two small
+        launches behind the verdict, outside the captured graph: the graph's launches only ever write `bn_pending`."""
+        if self._bn:
+            self.bn_running.copy_(self.bn_pending)
+            self.bn_nbt.add_(1)
+
+    def _forward_dncnn(self, x_nchw):
+        """DnCNN (archs/comp.py:16-33) in .train() mode: conv(4 -> nf, bias) + ReLU, (depth - 2) x [conv(nf -> nf, no bias), BatchNorm on
+        the batch statistics + ReLU (use_bn: False: ReLU)], conv(nf -> 4, no bias); x - out for `res`.  The first layer's input and the
+        last layer's output are padded to 32 channels, as the U-Nets' edge layers are."""
+        m, P = self.m, self.params
+        x = x_nchw.permute(0, 2, 3, 1).contiguous()
+        layers = list(m.dncnn)
+        last = len(layers) - 1
+        cur = F.relu(_Conv3x3.apply(_pad_c(x, 32), P['dncnn.0.weight'], P['dncnn.0.bias'], self.plan, 1, False))
+        acts = {1: cur.detach()} if getattr(self, 'keep_acts', False) else None      # (tests: the ReLU outputs by their index in `dncnn`)
+        i = 2
+        while i < last:
+            cur = _Conv3x3.apply(cur, P[f'dncnn.{i}.weight'], None, self.plan, 1, True)
+            i += 1
+            if i in self._bn:
+                cur = _BatchNormRelu.apply(cur, P[f'dncnn.{i}.weight'], P[f'dncnn.{i}.bias'], self._bn[i], self.plan)
+                i += 1
+            else:
+                cur = F.relu(cur)
+            if acts is not None:
+                acts[i] = cur.detach()
+            i += 1                                           # (the ReLU's slot in the reference's numbering)
+        out = _Conv3x3.apply(cur, P[f'dncnn.{last}.weight'], None, self.plan, 1, True)[..., :4]
+        if m.res:
+            out = x - out
+        self.last_acts = acts
+        return out.permute(0, 3, 1, 2)
+
     def forward(self, x_nchw, sigma=None):
         m, P = self.m, self.params
         if type(m).__name__ == 'UNetSeeInDark':
             return self._forward_unet(x_nchw)
+        if type(m).__name__ == 'DnCNN':
+            return self._forward_dncnn(x_nchw)
         snr = type(m).__name__ == 'SNRnet'                   # the same skeleton with SNR_Blocks (archs/Unet.py:288-378)
         if type(m).__name__ != 'GuidedResUnet' and not snr:
-            raise NotImplementedError(f"TrainStep: {type(m).__name__} (GuidedResUnet, SNRnet and UNetSeeInDark are built)")
+            raise NotImplementedError(f"TrainStep: {type(m).__name__} (GuidedResUnet, SNRnet, UNetSeeInDark and DnCNN are built)")
         block = self._block_snr if snr else self._block
         x = x_nchw.permute(0, 2, 3, 1).contiguous()
         B = x.shape[0]
@@ -982,6 +1115,7 @@ class TrainStep:
         if not math.isfinite(loss):
             raise L.YondHipError(f"TrainStep: the loss is {loss}: no update applied")
         self.t += 1
+        self._bn_commit()
         self.last_scale = S
         self._clean_steps = getattr(self, '_clean_steps', 0) + 1
         self.last_pred = g.pred.detach()
@@ -1065,6 +1199,7 @@ class TrainStep:
             raise L.YondHipError(f"TrainStep: the loss is {loss}: no update applied")
         L.check(lib.yond_adam_step_f32(L.ptr(self.arena), L.ptr(flat), L.ptr(self.adam_m), L.ptr(self.adam_v), self.arena.numel(),
                                        self.lr, self.betas[0], self.betas[1], self.eps, self.t, L.stream()), "yond_adam_step_f32")
+        self._bn_commit()
         self.plan.wbatch = None                              # (the gathered weights are those of before this update)
         self.m._plan = None                                  # the inference plan's packed weights are stale now
         return loss, grads

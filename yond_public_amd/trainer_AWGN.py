@@ -7,7 +7,8 @@ Same runfile schema (`dst*`, `arch`, `hyper`), same class / method names (`AWGN_
 change_eval_dst`), same checkpoint names and search order, same epoch loop: per batch `preprocess` -> forward -> loss ->
 backward -> Adam step -> running train PSNR; per epoch scheduler.step(), every `save_freq` epochs the state_dict, every
 `plot_freq` epochs a fast eval at sigma_list[1] with the best model kept.  What differs is the point of this build: forward,
-backward, loss and Adam run on the HIP kernels (yond_public_amd/train.py), one process per GPU with the gradients averaged
+backward, loss and Adam run on the HIP kernels (yond_public_amd/train.py; GuidedResUnet, SNRnet, UNetSeeInDark and -- single process --
+DnCNN with its BatchNorm layers on the batch statistics, runfiles/Gaussian/DnCNN_5to50_norm.yml), one process per GPU with the gradients averaged
 over RCCL in 25 MB buckets behind the backward pass (distributed.GradReducer) instead of torch DDP, every rank draws its own
 shard of the epoch's permutation (DistributedSampler's rule), and the evaluation forward is the inference engine.
 
@@ -495,6 +496,8 @@ class AWGN_Trainer:
             with open(metrics_path, 'rb') as f:
                 metrics = pkl.load(f)
         guided = 'guided' in self.args['arch']
+        was_training = self.net.training
+        self.net.eval()                                         # :196 -- DnCNN's BatchNorm: the running statistics, folded into the convolutions
         for k in range(len(self.dst_eval)):
             if self.src_eval is not None:
                 data = dict(self.src_eval.item(k, self.dst_eval.sigma), name=self.dst_eval.names[k])
@@ -512,6 +515,7 @@ class AWGN_Trainer:
             self.eval_psnr.update(res['PSNR'])
             self.eval_ssim.update(res['SSIM'])
             metrics[name] = [res['PSNR'], res['SSIM']]
+        self.net.train(was_training)
         if self.eval_psnr.avg >= self.best_psnr and epoch > 0:
             self.best_psnr = self.eval_psnr.avg
             log(f"Best PSNR is {self.best_psnr} now!!")
