@@ -354,6 +354,36 @@ int yond_fbi_out_f32(const float* f /*[N][2h][2w][nf]*/, int nf, const float* w,
                      float sigmoid_value, const float* x4 /*[N][h][w][4]; oc 2 only*/, int N, int h, int w_, float* dst4 /*[N][h][w][4]*/,
                      void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Training FBI_Net (csrc/fbinet_train.hip): the backward entries the step needs beside the forward kernels above.  Same tensors
+ * ([N][H][W][nf] float32, nf 32 | 64), same arithmetic: exact fp32 products (the fp32-input MFMA, or the exact float64 product of two
+ * float32), nothing rounded to half.  Every sum over pixels goes through per-workgroup partial sums in `ws` (16-byte aligned, at least
+ * yond_fbi_train_ws_bytes(nf, N, H, W) bytes: one workspace serves every entry at that shape) and a finish that adds them in float64
+ * in workgroup order: no float atomics, two calls give the same bits.
+ * yond_fbi_wgrad_f32: dwb = dW [taps][nf (co)][nf (ci)], then db [nf]:  dW_t[co][ci] = sum_{n,y,x} dz[n,y,x,co] x[n,y+dy_t,x+dx_t,ci]
+ *   over the live taps of set 0 | 1 (yond_fbi_tapconv_f32's, in its order) or set 2, a 1x1 convolution (one tap); reads outside the
+ *   frame are zero; db[co] = sum dz.  A workgroup accumulates yond_fbi_wgrad_rows(N, H) image rows (that many times W terms) in fp32.
+ * yond_fbi_prelu_f32: u = (a + b) / div (b NULL: a / div; div >= 1), y = u > 0 ? u : slope u; slope_n = nf (per channel) or 1.
+ *   u (may be NULL) receives the PReLU's input.
+ * yond_fbi_prelu_bwd_f32: du = dy (u > 0 ? 1 : slope) / div -- the gradient of a and of b alike --, dslope [slope_n] = sum of dy u
+ *   over u <= 0 (slope_n 1: over all channels).
+ * yond_fbi_first_bwd_f32: the first layer's dwb = dW [8 live taps, yond_pack_fbi_first_weight_f32's order][nf], then db [nf], from
+ *   dz [N][2h][2w][nf] and the packed batch x4.
+ * yond_fbi_out_bwd_f32: the output layer (yond_fbi_out_f32's arguments) from dpred4 [N][h][w][4]: df [N][2h][2w][nf] and
+ *   dwb [2 nf + 2] = dW row 0 [nf], dW row 1 [nf], db0, db1 (oc 1: row 1 and db1 are zero). */
+size_t yond_fbi_train_ws_bytes(int nf, int N, int H, int W);
+int yond_fbi_wgrad_rows(int N, int H);
+int yond_fbi_wgrad_f32(const float* x, const float* dz, int set, int nf, int N, int H, int W, float* dwb, void* ws, size_t ws_bytes,
+                       void* stream);
+int yond_fbi_prelu_f32(const float* a, const float* b /* or NULL */, float div, const float* slope, int slope_n, int nf, size_t npix,
+                       float* u /* or NULL */, float* y, void* stream);
+int yond_fbi_prelu_bwd_f32(const float* u, const float* dy, float div, const float* slope, int slope_n, int nf, size_t npix, float* du,
+                           float* dslope, void* ws, size_t ws_bytes, void* stream);
+int yond_fbi_first_bwd_f32(const float* x4, const float* dz, int N, int h, int w, int nf, float* dwb, void* ws, size_t ws_bytes, void* stream);
+int yond_fbi_out_bwd_f32(const float* f, int nf, const float* w, const float* b, int oc, int use_sigmoid, float sigmoid_value,
+                         const float* x4, const float* dpred4, int N, int h, int w_, float* df, float* dwb, void* ws, size_t ws_bytes,
+                         void* stream);
+
 /* Minimum and maximum of the bias-corrected stabilised value that yond_pack_vst_norm_f32 / _biaslut_f32 / _batch_f32 normalise
  * (the same device function, float64), over each of B Bayer frames [B][H][W] that share the constants and the LUT:
  * out [B][2] float64 = (min, max) -- the reference's `lower, upper = raw_vst.min(), raw_vst.max()` of its 'fbi' branch

@@ -78,6 +78,13 @@ PROTOTYPES = {
     "yond_fbi_tapconv_f32": [vp, vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp],
     "yond_fbi_rm_f32": [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, sz, vp, vp, i32, vp],
     "yond_fbi_out_f32": [vp, i32, vp, vp, i32, i32, f32, vp, i32, i32, i32, vp, vp],
+    "yond_fbi_train_ws_bytes": [i32, i32, i32, i32],
+    "yond_fbi_wgrad_rows": [i32, i32],
+    "yond_fbi_wgrad_f32": [vp, vp, i32, i32, i32, i32, i32, vp, vp, sz, vp],
+    "yond_fbi_prelu_f32": [vp, vp, f32, vp, i32, i32, sz, vp, vp, vp],
+    "yond_fbi_prelu_bwd_f32": [vp, vp, f32, vp, i32, i32, sz, vp, vp, vp, sz, vp],
+    "yond_fbi_first_bwd_f32": [vp, vp, i32, i32, i32, i32, vp, vp, sz, vp],
+    "yond_fbi_out_bwd_f32": [vp, i32, vp, vp, i32, i32, f32, vp, vp, i32, i32, i32, vp, vp, vp, sz, vp],
     "yond_vst_minmax_f32": [vp, i32, i32, i32, f64, f64, f64, vp, vp, i32, i32, vp, vp],
     "yond_maxpool2_f32": [vp, i32, i32, i32, i32, vp, vp],
     "yond_film_f32": [vp, i32, vp, vp, i32, vp],
@@ -172,7 +179,7 @@ PROTOTYPES = {
 _SIZE_T_RET = {"yond_select_ws_bytes", "yond_nle_ws_bytes", "yond_lut_ws_bytes", "yond_bias_lut_big_scratch", "yond_bias_points_scratch",
                "yond_conv_wgrad_ws_bytes", "yond_conv_wgrad_split_ws_bytes",
                "yond_est_head_ws_bytes", "yond_ransac_compact_ws_bytes", "yond_ransac_ws_bytes",
-               "yond_illum_ws_bytes", "yond_bn_train_ws_bytes"}
+               "yond_illum_ws_bytes", "yond_bn_train_ws_bytes", "yond_fbi_train_ws_bytes"}
 
 
 class YondHipError(RuntimeError):

@@ -14,22 +14,10 @@
 // channel 8 g + 4 h + e, so a lane's four consecutive steps read ONE 16-byte slot of its pixel -- and an accumulator tile is, as it
 // stands, the B operand of the next product over its channels (rm chains its two GEMMs without LDS or lane movement).
 #include "common.h"
+#include "fbi_taps.h"
 
 #define FBI_TH 8        // tapconv's pixel tile: 8 rows (two per wave) x 32 columns (the MFMA's 32 columns)
 #define FBI_TW 32
-
-// tap set 0: the 9 knight-and-centre taps of the masked 5x5 (archs/comp.py:281), set 1: centre and corners of the 3x3 at dilation 3 (:294)
-template <int SET> struct FbiTaps;
-template <> struct FbiTaps<0> {
-    static constexpr int N = 9, HALO = 2, K = 5, DIL = 1;
-    static constexpr int r[9] = {0, 0, 1, 1, 2, 3, 3, 4, 4};        // (row, column) in the 5x5 kernel
-    static constexpr int c[9] = {1, 3, 0, 4, 2, 0, 4, 1, 3};
-};
-template <> struct FbiTaps<1> {
-    static constexpr int N = 5, HALO = 3, K = 3, DIL = 3;
-    static constexpr int r[9] = {0, 0, 1, 2, 2, 0, 0, 0, 0};        // (row, column) in the 3x3 kernel
-    static constexpr int c[9] = {0, 2, 1, 0, 2, 0, 0, 0, 0};
-};
 
 __device__ __forceinline__ float prelu_f(float x, float s) { return x > 0.0f ? x : x * s; }
 

@@ -17,7 +17,9 @@ to multiples of 32, with every convolution -- forward, data gradient and weight 
 torch.autograd only strings the layers together (custom Functions) and differentiates the elementwise glue (SiLU, LeakyReLU,
 FiLM scale / shift and its three tiny sigma-MLPs, residual adds), which is <0.1 % of the step's arithmetic.
 Scope: GuidedResUnet, SNRnet and UNetSeeInDark (the nets the reference's runfiles/Gaussian/*.yml train) and the comparison denoiser DnCNN
-(archs/comp.py:3-33, runfiles/Gaussian/DnCNN_5to50_norm.yml: BatchNorm on the batch statistics with its backward, csrc/bn_train.hip, single process) / fp32; weights are re-packed on the host every step (fine at nf = 8 ... 32; a production loop would keep
+(archs/comp.py:3-33, runfiles/Gaussian/DnCNN_5to50_norm.yml: BatchNorm on the batch statistics with its backward, csrc/bn_train.hip, single process)
+and FBI_Net (archs/comp.py:264-648, runfiles/Gaussian/FBI_5to50_norm.yml: sparse-tap weight gradients and the PReLU backward, csrc/fbinet_train.hip,
+exact fp32 products throughout, single process) / fp32; weights are re-packed on the host every step (fine at nf = 8 ... 32; a production loop would keep
 packed weights resident).  Data-parallel: one process per GPU, every rank steps on its own batches, `GradReducer` averages the
 gradients in two 25 MB buckets launched from backward's hooks (the only collective of training: 44.7 MB per step).
 Pinned by tests/golden/train.npz (loss, gradients and updated weights of the reference's own step on the same inputs) and
@@ -492,6 +494,237 @@ def _bn_ws(plan, M, C):
     return ws
 
 
+# -- FBI_Net (csrc/fbinet.hip, csrc/fbinet_train.hip; DESIGN section 4 "D2t") ---------------------------------------------------
+def _fbi_ws(plan, nf, N, H, W):
+    """The FBI_Net reductions' partial sums: one workspace per plan, grown to the largest shape's need (every launch that uses it is on
+    the step's main stream, in order)."""
+    need = int(plan.lib.yond_fbi_train_ws_bytes(nf, N, H, W))
+    if not need:
+        raise L.YondHipError(f"FBI_Net on the HIP path takes nf 32 or 64, got nf = {nf} on {N} x {H} x {W}")
+    ws = getattr(plan, 'fbi_ws', None)
+    if ws is None or ws.numel() * 8 < need:
+        ws = plan.fbi_ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=plan.dev); plan.gen += 1   # (captured steps hold the old one)
+    return ws
+
+
+def _fbi_const(plan, nf):
+    """Unit slopes and a zero bias: PReLU(.; 1) is the identity bit for bit, so the fused forward kernels give the bare convolution."""
+    c = getattr(plan, 'fbi_const', None)
+    if c is None or c[0].numel() != nf:
+        c = plan.fbi_const = (torch.ones(nf, dtype=torch.float32, device=plan.dev), torch.zeros(nf, dtype=torch.float32, device=plan.dev))
+    return c
+
+
+def _fbi_gathered(plan, key, build):
+    """arena.index_select(map): a kernel's packed weights (and the bias behind them) as a fixed gather of arena elements, as _Packing.
+    `build()` returns the map as a host LongTensor of arena element numbers; it is computed once per key."""
+    maps = plan.__dict__.setdefault('fbi_maps', {})
+    m = maps.get(key)
+    if m is None:
+        m = maps[key] = build().to(plan.dev)
+    return plan.arena.index_select(0, m)
+
+
+def _arena_base(plan, p):
+    base = (p.data_ptr() - plan.arena.data_ptr()) // 4
+    assert 0 < base and base + p.numel() <= plan.arena.numel()
+    return base
+
+
+def _fbi_tap_ids(plan, w, tset, dgrad):
+    """The tap kernel's packed layout of `w` [nf][nf][K][K] (dgrad: of its flipped transpose -- the tap sets are point-symmetric, so the
+    data gradient is the same tap convolution) as arena element numbers: the host packer is run on the element numbers themselves."""
+    nf = w.shape[0]
+    ids = torch.arange(1, w.numel() + 1, dtype=torch.float32).reshape(w.shape)
+    if dgrad:
+        ids = ids.flip(2, 3).transpose(0, 1).contiguous()
+    out = np.empty(int(plan.lib.yond_fbi_taps(tset)) * nf * nf, np.float32)
+    L.check(plan.lib.yond_pack_fbi_tap_weight_f32(C.c_void_p(ids.numpy().ctypes.data), nf, tset, C.c_void_p(out.ctypes.data)), "yond_pack_fbi_tap_weight_f32")
+    return torch.from_numpy(out).round().long() - 1
+
+
+def _fbi_tapconv(plan, x, tset, wpk, bias, out):
+    """out = sum over the live taps of W_t x(. + d_t) + bias: yond_fbi_tapconv_f32 with unit slopes (its second output, the averaging
+    node on an operand that is not there, goes to a scratch tensor)."""
+    N, H, W, nf = x.shape
+    ones, _ = _fbi_const(plan, nf)
+    scratch = torch.empty_like(x)
+    L.check(plan.lib.yond_fbi_tapconv_f32(L.ptr(x), L.ptr(x), tset, nf, L.ptr(wpk), L.ptr(bias), L.ptr(ones), L.ptr(ones), N, H, W, L.ptr(out),
+                                          L.ptr(scratch), L.stream()), "yond_fbi_tapconv_f32")
+    return out
+
+
+def _fbi_wgrad(plan, x, dz, tset):
+    """(dW [taps][co][ci], db [co]) of a tap convolution (tset 2: a 1x1)."""
+    N, H, W, nf = x.shape
+    taps = 1 if tset == 2 else int(plan.lib.yond_fbi_taps(tset))
+    ws = _fbi_ws(plan, nf, N, H, W)
+    dwb = torch.empty(taps * nf * nf + nf, dtype=torch.float32, device=x.device)
+    L.check(plan.lib.yond_fbi_wgrad_f32(L.ptr(x), L.ptr(dz), tset, nf, N, H, W, L.ptr(dwb), L.ptr(ws), ws.numel() * 8, L.stream()), "yond_fbi_wgrad_f32")
+    return dwb[:taps * nf * nf].view(taps, nf, nf), dwb[taps * nf * nf:]
+
+
+class _FbiFirst(torch.autograd.Function):
+    """New1's convolution (archs/comp.py:264-275): packed batch x4 [N][h][w][4] -> z [N][2h][2w][nf], the 3x3 without its centre."""
+    LIVE = (0, 1, 2, 3, 5, 6, 7, 8)
+
+    @staticmethod
+    def forward(ctx, x4, w, b, plan):
+        N, h, wd, _ = x4.shape
+        nf = w.shape[0]
+
+        def ids():
+            wb, bb = _arena_base(plan, w), _arena_base(plan, b)
+            co = torch.arange(nf)
+            return torch.cat([(wb + co * 9 + k) for k in _FbiFirst.LIVE] + [bb + co])
+        wpk = _fbi_gathered(plan, (w.data_ptr(), 'first'), ids)
+        ones, _ = _fbi_const(plan, nf)
+        z = torch.empty((N, 2 * h, 2 * wd, nf), dtype=torch.float32, device=x4.device)
+        L.check(plan.lib.yond_fbi_first_f32(L.ptr(x4), N, h, wd, nf, L.ptr(wpk), L.ptr(wpk[8 * nf:]), L.ptr(ones), L.ptr(z), L.stream()), "yond_fbi_first_f32")
+        ctx.save_for_backward(x4)
+        ctx.plan, ctx.nf = plan, nf
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        x4, = ctx.saved_tensors
+        plan, nf = ctx.plan, ctx.nf
+        dz = dz.contiguous()
+        N, h, wd, _ = x4.shape
+        ws = _fbi_ws(plan, nf, N, 2 * h, 2 * wd)
+        dwb = torch.empty(9 * nf, dtype=torch.float32, device=dz.device)
+        L.check(plan.lib.yond_fbi_first_bwd_f32(L.ptr(x4), L.ptr(dz), N, h, wd, nf, L.ptr(dwb), L.ptr(ws), ws.numel() * 8, L.stream()), "yond_fbi_first_bwd_f32")
+        live = getattr(plan, 'fbi_live8', None)
+        if live is None:
+            live = plan.fbi_live8 = torch.tensor(_FbiFirst.LIVE, device=plan.dev)
+        dw = torch.zeros((nf, 9), dtype=torch.float32, device=dz.device)         # (the centre tap is dead: its gradient is zero)
+        dw.index_copy_(1, live, dwb[:8 * nf].view(8, nf).t())
+        return None, dw.view(nf, 1, 3, 3), dwb[8 * nf:], None
+
+
+class _FbiPrelu(torch.autograd.Function):
+    """y = PReLU((a [+ b]) / div; slope), slope per channel or ONE for all channels (new1.activation_new1): every PReLU of the net with
+    the averaging node in front of it.  The PReLU's input u is what the backward keeps (slopes start at 0 and may be negative: u cannot be
+    recovered from y); `plan.fbi_u` names it for TrainStep.keep_acts."""
+
+    @staticmethod
+    def forward(ctx, a, b, slope, plan, div):
+        a = a.contiguous()
+        b = None if b is None else b.contiguous()
+        nf = a.shape[-1]
+        y = torch.empty_like(a)
+        u = torch.empty_like(a) if (b is not None or div != 1) else None
+        L.check(plan.lib.yond_fbi_prelu_f32(L.ptr(a), L.ptr(b), float(div), L.ptr(slope), slope.numel(), nf, a.numel() // nf, L.ptr(u), L.ptr(y),
+                                            L.stream()), "yond_fbi_prelu_f32")
+        u = a if u is None else u
+        ctx.save_for_backward(u, slope)
+        ctx.plan, ctx.div, ctx.two = plan, float(div), b is not None
+        plan.fbi_u = u
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        u, slope = ctx.saved_tensors
+        plan = ctx.plan
+        dy = dy.contiguous()
+        N, H, W, nf = u.shape
+        ws = _fbi_ws(plan, nf, N, H, W)
+        du, ds = torch.empty_like(u), torch.empty(slope.numel(), dtype=torch.float32, device=u.device)
+        L.check(plan.lib.yond_fbi_prelu_bwd_f32(L.ptr(u), L.ptr(dy), ctx.div, L.ptr(slope), slope.numel(), nf, u.numel() // nf, L.ptr(du), L.ptr(ds),
+                                                L.ptr(ws), ws.numel() * 8, L.stream()), "yond_fbi_prelu_bwd_f32")
+        return du, (du if ctx.two else None), ds.view(slope.shape), None, None
+
+
+class _FbiTapConv(torch.autograd.Function):
+    """New2 / New3 (archs/comp.py:277-301): z = sum over the LIVE taps of W_t x(. + d_t) + b on [N][H][W][nf].  The gradient of a dead
+    tap is zero (the reference's autograd returns a dense one and its next forward zeroes the tap again: DESIGN 4 D2t)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, plan, tset):
+        x = x.contiguous()
+        nf = w.shape[0]
+        wb = _fbi_gathered(plan, (w.data_ptr(), 'tap', tset),
+                           lambda: torch.cat([_fbi_tap_ids(plan, w, tset, False) + _arena_base(plan, w), _arena_base(plan, b) + torch.arange(nf)]))
+        z = _fbi_tapconv(plan, x, tset, wb, wb[wb.numel() - nf:], torch.empty_like(x))
+        ctx.save_for_backward(x, w)
+        ctx.plan, ctx.tset = plan, tset
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        x, w = ctx.saved_tensors
+        plan, tset = ctx.plan, ctx.tset
+        dz = dz.contiguous()
+        nf, K = w.shape[0], w.shape[2]
+        dwt, db = _fbi_wgrad(plan, x, dz, tset)
+        # where the live taps sit in the K x K kernel: the packer's own order (element (co 0, ci 0) of tap t opens the tap's block)
+        pos = plan.__dict__.setdefault('fbi_pos', {}).get(tset)
+        if pos is None:
+            ids = _fbi_tap_ids(plan, w, tset, False)
+            pos = plan.fbi_pos[tset] = ids[::2 * (nf // 32) * 256][:dwt.shape[0]].to(plan.dev)
+        dw = torch.zeros((nf, nf, K * K), dtype=torch.float32, device=dz.device)
+        dw.index_copy_(2, pos, dwt.permute(1, 2, 0))
+        wpk = _fbi_gathered(plan, (w.data_ptr(), 'tap_dgrad', tset), lambda: _fbi_tap_ids(plan, w, tset, True) + _arena_base(plan, w))
+        dx = _fbi_tapconv(plan, dz, tset, wpk, _fbi_const(plan, nf)[1], torch.empty_like(dz))
+        return dx, dw.view(nf, nf, K, K), db, None, None
+
+
+class _FbiConv1x1(torch.autograd.Function):
+    """A residual module's 1x1 convolution nf -> nf (archs/comp.py:303-322): forward and data gradient on the fp32-input MFMA convolution
+    (yond_conv2d_f32, algo 0, as _Conv1x1 on its fp32 path), weight and bias gradient by the one-tap set of yond_fbi_wgrad_f32 (float64
+    finish in a fixed order, where _Conv1x1's column sum uses float atomics)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, plan):
+        x = x.contiguous()
+        N, H, W, nf = x.shape
+        y = _conv_fwd(plan, w, b, 1, 1, [nf], [x], N, H, W)
+        ctx.save_for_backward(x, w)
+        ctx.plan = plan
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        plan = ctx.plan
+        dy = dy.contiguous()
+        N, H, W, nf = x.shape
+        dwt, db = _fbi_wgrad(plan, x, dy, 2)
+        dx = _conv_fwd(plan, w, None, 1, 1, [nf], [dy], N, H, W, role='dgrad', xf=lambda t: t[:, :, 0, 0].t().contiguous()[:, :, None, None])
+        return dx, dwt.view(nf, nf, 1, 1), db, None
+
+
+class _FbiOut(torch.autograd.Function):
+    """The output layer (archs/comp.py:598, 624, 642-646): y = W f + b, optional sigmoid_value * sigmoid on y0, pred = y0 x + y1 (`res`) or
+    y0, stored as packed Bayer [N][h][w][4].  x is a constant."""
+
+    @staticmethod
+    def forward(ctx, f, w, b, x4, plan, sigmoid, sigmoid_value):
+        f = f.contiguous()
+        oc, nf = w.shape[0], w.shape[1]
+        wb = _fbi_gathered(plan, (w.data_ptr(), 'out'),
+                           lambda: torch.cat([_arena_base(plan, w) + torch.arange(oc * nf), _arena_base(plan, b) + torch.arange(oc)]))
+        N, h, wd, _ = x4.shape
+        y4 = torch.empty_like(x4)
+        L.check(plan.lib.yond_fbi_out_f32(L.ptr(f), nf, L.ptr(wb), L.ptr(wb[oc * nf:]), oc, int(sigmoid), float(sigmoid_value), L.ptr(x4) if oc == 2 else None,
+                                          N, h, wd, L.ptr(y4), L.stream()), "yond_fbi_out_f32")
+        ctx.save_for_backward(f, wb, x4)
+        ctx.plan, ctx.cfg = plan, (oc, nf, int(sigmoid), float(sigmoid_value))
+        return y4
+
+    @staticmethod
+    def backward(ctx, dpred4):
+        f, wb, x4 = ctx.saved_tensors
+        plan, (oc, nf, sigmoid, sv) = ctx.plan, ctx.cfg
+        dpred4 = dpred4.contiguous()
+        N, h, wd, _ = x4.shape
+        ws = _fbi_ws(plan, nf, N, 2 * h, 2 * wd)
+        df, dwb = torch.empty_like(f), torch.empty(2 * nf + 2, dtype=torch.float32, device=f.device)
+        L.check(plan.lib.yond_fbi_out_bwd_f32(L.ptr(f), nf, L.ptr(wb), L.ptr(wb[oc * nf:]), oc, sigmoid, sv, L.ptr(x4) if oc == 2 else None, L.ptr(dpred4),
+                                              N, h, wd, L.ptr(df), L.ptr(dwb), L.ptr(ws), ws.numel() * 8, L.stream()), "yond_fbi_out_bwd_f32")
+        return df, dwb[:oc * nf].view(oc, nf, 1, 1), dwb[2 * nf:2 * nf + oc], None, None, None, None
+
+
 class _FilmMLP(torch.autograd.Function):
     """The sigma-conditioning of a guided block (archs/modules.py:170-178: gamma = Conv2d(1, C, 1) -> SiLU -> Conv2d(C, C, 1),
     beta = SiLU -> Conv2d(C, C, 1) on t [B][1][1][1]) as ONE kernel forward and two backward (yond_film_mlp_fwd_f32 / _bwd_f32)
@@ -682,8 +915,8 @@ class _ConvT2x2(torch.autograd.Function):
 
 
 class TrainStep:
-    """One optimisation step of a yond_public_amd.archs.GuidedResUnet, SNRnet, UNetSeeInDark or DnCNN (parameter names / shapes of the
-    reference).  A step always trains: DnCNN's BatchNorm layers normalise with the batch statistics whatever module.training says
+    """One optimisation step of a yond_public_amd.archs.GuidedResUnet, SNRnet, UNetSeeInDark, DnCNN or FBI_Net (parameter names / shapes
+    of the reference; FBI_Net: _forward_fbi, batches are the trainer's packed [N][4][h][w]).  A step always trains: DnCNN's BatchNorm layers normalise with the batch statistics whatever module.training says
     (`net(x)` itself keeps refusing .train() mode: inference folds the running statistics).  BatchNorm and the loss scale: the backward is
     linear in dout, so dgamma / dbeta come out at scale S and are unscaled with the flat gradient -- nothing special; the forward does not
     depend on S, so the attempts of a redone step leave the same pending running statistics, committed once (_bn_commit)."""
@@ -716,10 +949,16 @@ class TrainStep:
             raise L.YondHipError("TrainStep: DnCNN with BatchNorm layers under a process group is not built: the reference's DDP normalises every "
                                  "rank's batch with its own statistics and broadcasts rank 0's buffers, and neither that exchange nor SyncBatchNorm "
                                  "exists on the HIP path (train it in one process, or with use_bn: False)")
+        fbi = type(module).__name__ == 'FBI_Net'
+        if fbi and ddp is not False and D._active():
+            raise L.YondHipError("TrainStep: FBI_Net under a process group is not built: the gradient exchange has never been run with this "
+                                 "arch (train it in one process, or pass ddp=False)")
         self.plan = _plan(self.dev)
         if conv not in ('split', 'fp32'):
             raise ValueError(f"conv must be 'split' or 'fp32', got {conv!r}")
-        self.plan.train_conv = conv
+        # FBI_Net: the module's precision ('fp32-mfma', the only one built) decides, `conv` is not consulted: every product exact fp32,
+        # so no operand range, loss scale 1, no redo path
+        self.plan.train_conv = 'fp32' if fbi else conv
         self.loss_scale = loss_scale
         self.lr, self.betas, self.eps = lr, betas, eps
         self.charbonnier = bool(charbonnier)
@@ -894,15 +1133,56 @@ class TrainStep:
         self.last_acts = acts
         return out.permute(0, 3, 1, 2)
 
+    def _forward_fbi(self, x_nchw):
+        """FBI_Net (archs/comp.py:568-648, case 'FBI_Net') for training: the inference forward of fbinet.FBINetPlan, unfused so that every
+        PReLU's input survives to the backward.  x_nchw: the trainer's packed batch [N][4][h][w], read as the mosaic [N][1][2h][2w]
+        (channel 2 (y & 1) + (x & 1) of the packed pixel); returns packed [N][4][h][w].  With `keep_acts`, `last_acts` maps the name of each
+        PReLU's slope parameter (in forward order: new1.activation_new1, then per layer activation_new1, activation_new2 and the residual
+        module's activation1, activation2 -- new1 has no activation_new2 --, then activation and the last module's two) to that PReLU's
+        input [N][H][W][nf]."""
+        m, P, plan = self.m, self.params, self.plan
+        if x_nchw.dim() != 4 or x_nchw.shape[1] != 4:
+            # (the kernels read four floats per packed pixel: anything else must stop here, before a launch)
+            raise NotImplementedError(f"TrainStep: FBI_Net steps on the trainer's packed batches [N][4][h][w], got {tuple(x_nchw.shape)} "
+                                      "(a step on the one-channel mosaic [N][1][H][W] the module's own forward takes is not built: pack it)")
+        x4 = x_nchw.permute(0, 2, 3, 1).contiguous()
+        acts = {} if getattr(self, 'keep_acts', False) else None
+
+        def prelu(name, a, b=None, div=1):
+            y = _FbiPrelu.apply(a, b, P[name + '.weight'], plan, div)
+            if acts is not None:
+                acts[name + '.weight'] = plan.fbi_u.detach()
+            return y
+
+        def rm(pre, v):
+            r = pre + 'residual_module.'
+            h = prelu(r + 'activation1', _FbiConv1x1.apply(v, P[r + 'conv1_1by1.weight'], P[r + 'conv1_1by1.bias'], plan))
+            return prelu(r + 'activation2', v, _FbiConv1x1.apply(h, P[r + 'conv2_1by1.weight'], P[r + 'conv2_1by1.bias'], plan), 2)
+        n = prelu('new1.activation_new1', _FbiFirst.apply(x4, P['new1.new1.conv1.weight'], P['new1.new1.conv1.bias'], plan))
+        o = rm('new1.', n)
+        total = o
+        for i in range(m.num_layers - 1):
+            pre, conv, tset = ('new2.', 'new2', 0) if i == 0 else (f'new_{i - 1}.', 'new3', 1)
+            n = prelu(pre + 'activation_new1', _FbiTapConv.apply(n, P[f'{pre}{conv}.conv1.weight'], P[f'{pre}{conv}.conv1.bias'], plan, tset))
+            o = rm(pre, prelu(pre + 'activation_new2', n, o, 2))
+            total = total + o
+        f = rm('', prelu('activation', total, None, m.num_layers))
+        y4 = _FbiOut.apply(f, P['output_layer.weight'], P['output_layer.bias'], x4, plan, m.output_type == 'sigmoid', m.sigmoid_value)
+        plan.fbi_u = None
+        self.last_acts = acts
+        return y4.permute(0, 3, 1, 2)
+
     def forward(self, x_nchw, sigma=None):
         m, P = self.m, self.params
         if type(m).__name__ == 'UNetSeeInDark':
             return self._forward_unet(x_nchw)
         if type(m).__name__ == 'DnCNN':
             return self._forward_dncnn(x_nchw)
+        if type(m).__name__ == 'FBI_Net':
+            return self._forward_fbi(x_nchw)
         snr = type(m).__name__ == 'SNRnet'                   # the same skeleton with SNR_Blocks (archs/Unet.py:288-378)
         if type(m).__name__ != 'GuidedResUnet' and not snr:
-            raise NotImplementedError(f"TrainStep: {type(m).__name__} (GuidedResUnet, SNRnet, UNetSeeInDark and DnCNN are built)")
+            raise NotImplementedError(f"TrainStep: {type(m).__name__} (GuidedResUnet, SNRnet, UNetSeeInDark, DnCNN and FBI_Net are built)")
         block = self._block_snr if snr else self._block
         x = x_nchw.permute(0, 2, 3, 1).contiguous()
         B = x.shape[0]

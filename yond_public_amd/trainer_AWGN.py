@@ -8,7 +8,8 @@ change_eval_dst`), same checkpoint names and search order, same epoch loop: per 
 backward -> Adam step -> running train PSNR; per epoch scheduler.step(), every `save_freq` epochs the state_dict, every
 `plot_freq` epochs a fast eval at sigma_list[1] with the best model kept.  What differs is the point of this build: forward,
 backward, loss and Adam run on the HIP kernels (yond_public_amd/train.py; GuidedResUnet, SNRnet, UNetSeeInDark and -- single process --
-DnCNN with its BatchNorm layers on the batch statistics, runfiles/Gaussian/DnCNN_5to50_norm.yml), one process per GPU with the gradients averaged
+DnCNN with its BatchNorm layers on the batch statistics, runfiles/Gaussian/DnCNN_5to50_norm.yml, and the blind-spot denoiser FBI_Net,
+runfiles/Gaussian/FBI_5to50_norm.yml: trained on the packed batches read as mosaics, evaluated by its own mosaic forward), one process per GPU with the gradients averaged
 over RCCL in 25 MB buckets behind the backward pass (distributed.GradReducer) instead of torch DDP, every rank draws its own
 shard of the epoch's permutation (DistributedSampler's rule), and the evaluation forward is the inference engine.
 
@@ -507,10 +508,15 @@ class AWGN_Trainer:
                 imgs_lr, imgs_hr, sigma = self.preprocess({'lr': data['lr'][None], 'hr': data['hr'][None], 'sigma': data['sigma']},
                                                           mode='eval', preprocess=False)
             name = data['name'] + (f"_K{float(data['K']):.3g}" if 'K' in data else f'_sig{int(sigma.item() * 255)}')
-            pad = imgs_lr.shape[-1] % 16 != 0                  # :220-225 (the reference calls a guided net without sigma there)
-            x = torch.nn.functional.pad(imgs_lr, (4, 4, 4, 4), mode='reflect') if pad else imgs_lr
-            imgs_dn = self.net(x, sigma) if guided else self.net(x)
-            imgs_dn = imgs_dn[..., 4:-4, 4:-4] if pad else imgs_dn
+            if self.arch['name'] == 'FBI_Net':
+                # the module's own inference forward takes the one-channel mosaic, unpadded as behind the VST's `fbi` branch
+                # (YOND_SIDD.py:266-279); the clamp to [0, 1] is the metric's, below
+                imgs_dn = _mosaic_to_packed(self.net(_packed_to_mosaic(imgs_lr)))
+            else:
+                pad = imgs_lr.shape[-1] % 16 != 0              # :220-225 (the reference calls a guided net without sigma there)
+                x = torch.nn.functional.pad(imgs_lr, (4, 4, 4, 4), mode='reflect') if pad else imgs_lr
+                imgs_dn = self.net(x, sigma) if guided else self.net(x)
+                imgs_dn = imgs_dn[..., 4:-4, 4:-4] if pad else imgs_dn
             res = quality_assess(imgs_dn.clamp(0, 1) * 255.0, (imgs_hr * 255.0).clamp(0, 255), data_range=255)
             self.eval_psnr.update(res['PSNR'])
             self.eval_ssim.update(res['SSIM'])
@@ -525,6 +531,17 @@ class AWGN_Trainer:
             with open(metrics_path, 'wb') as f:
                 pkl.dump(metrics, f)
         return metrics
+
+
+def _packed_to_mosaic(x):
+    """[N][4][h][w], channel 2 dy + dx -> the Bayer mosaic [N][1][2h][2w]."""
+    N, _, h, w = x.shape
+    return x.reshape(N, 2, 2, h, w).permute(0, 3, 1, 4, 2).reshape(N, 1, 2 * h, 2 * w).contiguous()
+
+
+def _mosaic_to_packed(m):
+    N, _, H, W = m.shape
+    return m.reshape(N, H // 2, 2, W // 2, 2).permute(0, 2, 4, 1, 3).reshape(N, 4, H // 2, W // 2).contiguous()
 
 
 def _atomic_save(obj, path):
